@@ -6,34 +6,47 @@ bus-bw at 1/2/4/8 amd.com/gpu" (configs 3 and 4).  One process per GPU, and
 ``torch.distributed`` over RCCL at every N (a 1-rank communicator at N = 1,
 so the all-reduce is a real ``ncclAllReduce`` there too).
 
+A plain run (``bench.py --gpus N --steps K --warmup W``) does only what the
+headline figure needs: it builds the operands, warms up, times the K steps,
+writes the outputs if ``--dump-outputs DIR`` is given and prints the result
+line.  Everything else below (the correctness gate, the per-launch event
+pass, the hipBLASLt A/B, the other sizes and the RCCL all-reduce sweep) runs
+only with ``--full``; without it those fields of the result line are null.
+
 Protocol (BASELINE.md "Measurement protocol"):
 
 * a *step* is one 8192^3 bf16 GEMM on this rank's GPU through the hand-written
   CDNA4 MFMA kernel (``native/kernels/gemm_bf16.hip``), random uniform
-  [-1, 1) operands (random data, never zeros: the chip clocks higher on zeros);
-* correctness gate: the WHOLE output of the first launch and of the last timed
-  launch is compared with an fp32 ``torch.matmul`` on the device, tolerance
-  2^-7 * max|ref| (bf16 output rounding is 2^-8 relative);
+  [-1, 1) operands (random data, never zeros: the chip clocks higher on zeros),
+  seeded per rank: the same arguments give the same operands in every run;
 * warm-up: ``--warmup`` launches, then more until ``--warmup-s`` (default 2 s)
   of back-to-back launches have run, whatever ``--warmup`` says (the GPU
   ramps its clock over ~1 s; a 5-launch warm-up times a cold chip);
 * exactly K timed steps bracketed by a barrier and ``torch.cuda.synchronize()``
   on both sides; the slowest rank's wall time gives ``value`` = whole-job
-  TFLOP/s = N x 2MNK x K / max-rank time.  The K launches run back to back
-  between one hipEvent pair (``event_span_ms_per_step``); a second pass of K
-  launches with an event between every two gives the per-launch median
-  (event records between launches cost ~1 % at 8192^3, so they stay out of
-  the timed region);
-* hipBLASLt (``torch.mm``) on the same operands is timed A/B-interleaved with
+  TFLOP/s = N x 2MNK x K / max-rank time and ``ms_per_step``.  The K launches
+  run back to back between one hipEvent pair (``event_span_ms_per_step``);
+* ``--dump-outputs DIR``: after the timed steps each rank writes the output of
+  its last timed launch as ``DIR/gemm_out_rank<r>.npy`` (float32; the whole
+  matrix when all ranks' fit in 48 MB, else a fixed seeded sample of its
+  elements, the same elements in every run);
+* ``--full``, correctness gate: the WHOLE output of the first launch and of
+  the last timed launch is compared with an fp32 ``torch.matmul`` on the
+  device, tolerance 2^-7 * max|ref| (bf16 output rounding is 2^-8 relative);
+* ``--full``: a second pass of K launches with an event between every two
+  gives the per-launch median (event records between launches cost ~1 % at
+  8192^3, so they stay out of the timed region);
+* ``--full``: hipBLASLt (``torch.mm``) on the same operands is timed A/B-interleaved with
   the hand-written kernel in blocks of back-to-back launches, one event pair
   per block (context, not the metric);
-* RCCL all-reduce (sum, bf16): a correctness check, then a 1 MiB - 1 GiB size
+* ``--full``: RCCL all-reduce (sum, bf16): a correctness check, then a 1 MiB - 1 GiB size
   sweep with algbw = bytes/t and busbw = algbw * 2(n-1)/n (0 at n = 1 by
   definition); the slowest rank's time per size.
 
-``--mode ddp`` runs the Llama-3-8B DDP training step (config 5) instead.
+``--mode ddp`` runs the Llama-3-8B DDP training step (config 5) instead
+(``--dump-outputs`` writes its per-step losses as ``losses.npy``).
 
-Run:  python bench.py [--gpus N --steps K --warmup W]
+Run:  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
       python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 \\
              bench.py --gpus N
 On a host without a GPU (the CPU test tier) the same code runs over gloo with
@@ -161,6 +174,41 @@ def _full_check(A, Bt, C):
     tol = 2.0 ** -7 * ref.abs().max().item()
     del ref
     return err, tol
+
+
+DUMP_BUDGET_BYTES = 48 << 20   # float32 bytes written by all ranks together
+DUMP_SAMPLE_SEED = 20240229
+
+
+def dump_sample_index(numel: int, world: int):
+    """Flat element indices of one rank's output that ``--dump-outputs``
+    writes: None (everything) when all ranks' float32 outputs fit in the
+    budget, else a fixed seeded sample (with repeats), the same for every
+    rank, run and build."""
+    import torch
+    keep = DUMP_BUDGET_BYTES // 4 // max(world, 1)
+    if numel <= keep:
+        return None
+    g = torch.Generator(device="cpu")
+    g.manual_seed(DUMP_SAMPLE_SEED)
+    return torch.randint(0, numel, (keep,), generator=g, dtype=torch.int64)
+
+
+def dump_output(path_dir: str, name: str, C, world: int) -> dict:
+    """Write tensor ``C`` (whole, or its seeded sample) as float32
+    ``path_dir/name.npy``; returns what was written."""
+    import numpy as np
+    os.makedirs(path_dir, exist_ok=True)
+    flat = C.reshape(-1)
+    idx = dump_sample_index(flat.numel(), world)
+    if idx is None:
+        arr = C.float().cpu().numpy()
+    else:
+        arr = flat[idx.to(flat.device)].float().cpu().numpy()
+    np.save(os.path.join(path_dir, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float32))
+    return {"file": name + ".npy", "dtype": "float32", "elements": int(arr.size),
+            "of": int(flat.numel()),
+            "sample": None if idx is None else f"torch.randint, cpu generator seed {DUMP_SAMPLE_SEED}"}
 
 
 def allreduce_sizes(args, world) -> list[int]:
@@ -347,7 +395,7 @@ def run_validator(args) -> dict:
     A = (torch.rand((M, K), device=dev, generator=g) * 2 - 1).to(torch.bfloat16)
     Bt = (torch.rand((N, K), device=dev, generator=g) * 2 - 1).to(torch.bfloat16)
     C = torch.empty((M, N), device=dev, dtype=torch.bfloat16)
-    C_ref = torch.empty((M, N), device=dev, dtype=torch.bfloat16)
+    C_ref = torch.empty((M, N), device=dev, dtype=torch.bfloat16) if args.full else None
 
     def mxk():
         gemm_bf16_tn(A, Bt, C)
@@ -355,19 +403,22 @@ def run_validator(args) -> dict:
     def blas():
         torch.mm(A, Bt.t(), out=C_ref)
 
-    # correctness gate before timing: the whole output vs fp32
-    C.zero_()
-    mxk()
-    _sync(dev)
-    err0, tol = _full_check(A, Bt, C)
-    if not err0 <= tol:
-        raise SystemExit(f"GEMM self-check failed: max|err| {err0} > {tol} (2^-7 max|ref|)")
-    _log(rank, f"[bench] GEMM {M}x{N}x{K} bf16 full-output check ok "
-               f"(max err {err0:.3g} <= {tol:.3g}); warmup >= {args.warmup} launches "
+    err0 = tol = None
+    if args.full:
+        # correctness gate before timing: the whole output vs fp32
+        C.zero_()
+        mxk()
+        _sync(dev)
+        err0, tol = _full_check(A, Bt, C)
+        if not err0 <= tol:
+            raise SystemExit(f"GEMM self-check failed: max|err| {err0} > {tol} (2^-7 max|ref|)")
+        _log(rank, f"[bench] GEMM {M}x{N}x{K} bf16 full-output check ok "
+                   f"(max err {err0:.3g} <= {tol:.3g})")
+        blas()   # both kernels launched before the warm-up so neither is timed cold
+    _log(rank, f"[bench] GEMM {M}x{N}x{K} bf16: warmup >= {args.warmup} launches "
                f"and >= {args.warmup_s} s, steps {args.steps}")
 
-    # time-floored warm-up; both kernels launched so neither is timed cold
-    blas()
+    # time-floored warm-up
     t_w = time.perf_counter()
     n_warm = 0
     while True:
@@ -398,28 +449,35 @@ def run_validator(args) -> dict:
     _sync(dev)
     span_ms = timer.elapsed_ms(span)[0]
     dt_max = _max_over_ranks(dt, dev)
-
-    # per-launch hipEvent times of another K launches (the median is reported
-    # beside the wall-clock mean; not part of the headline)
-    marks = timer.marks(args.steps + 1)
-    for i in range(args.steps):
-        timer.record(marks, i)
-        mxk()
-    timer.record(marks, args.steps)
-    step_ms = timer.elapsed_ms(marks)
     flops = 2.0 * M * N * K
     per_gpu_tflops = flops * args.steps / dt / 1e12
     agg_tflops = world * flops * args.steps / dt_max / 1e12
-    ev_med = statistics.median(step_ms)
 
-    # the output of the last timed launch, whole, vs fp32
-    err1, _ = _full_check(A, Bt, C)
-    if not err1 <= tol:
-        raise SystemExit(f"GEMM check after the timed loop failed: max|err| {err1} > {tol}")
+    # what the last timed launch wrote, before anything else touches C
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_output(args.dump_outputs, f"gemm_out_rank{rank}", C, world)
+
+    ev_med = err1 = None
+    if args.full:
+        # per-launch hipEvent times of another K launches (the median is reported
+        # beside the wall-clock mean; not part of the headline)
+        marks = timer.marks(args.steps + 1)
+        for i in range(args.steps):
+            timer.record(marks, i)
+            mxk()
+        timer.record(marks, args.steps)
+        step_ms = timer.elapsed_ms(marks)
+        ev_med = statistics.median(step_ms)
+
+        # the output of the last timed launch, whole, vs fp32
+        err1, _ = _full_check(A, Bt, C)
+        if not err1 <= tol:
+            raise SystemExit(f"GEMM check after the timed loop failed: max|err| {err1} > {tol}")
 
     # A/B-interleaved hipBLASLt under the same event protocol
     ab = None
-    if not args.no_reference:
+    if args.full and not args.no_reference:
         # blocks of n_ab back-to-back launches, one event pair per block (the
         # same protocol as the timed region), kernels alternating block by block
         n_ab = max(args.steps, 20)
@@ -440,8 +498,8 @@ def run_validator(args) -> dict:
               "hipblaslt_tflops": round(flops / m_blas / 1e9, 2),
               "mxk_over_hipblaslt": round(m_blas / m_mxk, 4)}
 
-    sizes_ab = [] if args.no_reference else ab_other_sizes(args, dev, timer)
-    ar = None if args.no_allreduce else run_allreduce(args, dev, world, rank)
+    sizes_ab = ab_other_sizes(args, dev, timer) if args.full and not args.no_reference else []
+    ar = run_allreduce(args, dev, world, rank) if args.full and not args.no_allreduce else None
 
     return {
         "metric": METRIC,
@@ -464,9 +522,12 @@ def run_validator(args) -> dict:
         "warmup_launches": n_warm,
         "warmup_s": round(warmup_s, 3),
         "event_span_ms_per_step": round(span_ms / args.steps, 4),
-        "event_median_ms": round(ev_med, 4),
-        "event_median_tflops": round(flops / ev_med / 1e9, 2),
-        "gemm_check": {"max_abs_err_first": err0, "max_abs_err_after_timed": err1,
+        "full": bool(args.full),
+        "outputs": dumped,
+        "event_median_ms": None if ev_med is None else round(ev_med, 4),
+        "event_median_tflops": None if ev_med is None else round(flops / ev_med / 1e9, 2),
+        "gemm_check": None if not args.full else
+                      {"max_abs_err_first": err0, "max_abs_err_after_timed": err1,
                        "tolerance": tol, "elements": M * N, "reference": "fp32 torch.matmul"},
         "hipblaslt_ab": ab,
         "hipblaslt_tflops_same_shape": None if ab is None else ab["hipblaslt_tflops"],
@@ -483,6 +544,11 @@ def main(argv=None) -> int:
     p.add_argument("--warmup", type=int, default=None)
     p.add_argument("--warmup-s", type=float, default=2.0,
                    help="validator mode: minimum seconds of warm-up launches")
+    p.add_argument("--full", action="store_true",
+                   help="validator mode: also run the correctness gate, the per-launch event "
+                        "pass, the hipBLASLt A/B, the other sizes and the all-reduce sweep")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write what the last timed step computed as DIR/<name>.npy (float32)")
     p.add_argument("--mode", choices=["validator", "ddp"], default="validator")
     p.add_argument("--size", type=int, default=8192, help="GEMM M=N=K (validator mode)")
     p.add_argument("--allreduce-mib", type=int, default=256, help="headline all-reduce size")
@@ -547,6 +613,11 @@ def main(argv=None) -> int:
             args.warmup = 3
         from mxk8s.train.ddp_llama import run_ddp_bench
         out = run_ddp_bench(args)
+        if args.dump_outputs and rank == 0:
+            import numpy as np
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "losses.npy"),
+                    np.asarray(out["losses"], dtype=np.float64))
 
     if rccl_vars is not None:
         out["rccl_env"] = {"profile": args.rccl_profile, "vars": rccl_vars}

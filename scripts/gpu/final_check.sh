@@ -20,5 +20,5 @@ step() {   # name, seconds, command...
 }
 step pytest_gpu 900 python3 -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread -p no:cacheprovider
 step smoke 300 python3 -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')"
-step bench_driver_args 300 python3 bench.py --steps 20 --warmup 5
+step bench_driver_args 300 python3 bench.py --full --steps 20 --warmup 5
 step bench_ddp 400 python3 bench.py --mode ddp --steps 10 --warmup 3

@@ -9,7 +9,7 @@
 #   pytest        the full GPU tier                       [PYTEST_K: -k filter]
 #   pytest_exp    A/B-record kernels on the experiments library [PYTEST_K]
 #   smoke         __graft_entry__.smoke()
-#   bench         bench.py at the driver's arguments (--steps 20 --warmup 5)
+#   bench         bench.py --full at the driver's arguments (--steps 20 --warmup 5)
 #   bench_ddp     bench.py --mode ddp                      [DDP_STEPS, DDP_ENV]
 #   gemm_ab       A/B of TN schedules                      [VARIANTS, SIZES, EXP=1]
 #   layouts_ab    step-shape A/B of the layout kernel      [VARIANTS]
@@ -19,7 +19,7 @@
 #   contention    DDP step beside a CU-pinned HBM streamer  [CONT_CUS, CONT_PLACE]
 #   ddp_gloo2     the multi-rank DDP step (ZeRO-1) rehearsed: 2 gloo ranks on one GPU,
 #                 2 Llama-3-8B layers (NOT the headline config)
-#   validator_gloo2  bench.py validator mode, 2 gloo ranks on one GPU
+#   validator_gloo2  bench.py --full validator mode, 2 gloo ranks on one GPU
 #   ddp_l2        the same 2-layer step on one rank (the reference for ddp_gloo2)
 set -u
 cd "${GRAFT_REPO_ROOT:-.}"
@@ -60,7 +60,7 @@ for step in "$@"; do
     smoke)
       run smoke 300 python3 -c "import __graft_entry__ as g; g.smoke()" ;;
     bench)
-      run bench 300 python3 bench.py --steps 20 --warmup 5 ;;
+      run bench 300 python3 bench.py --full --steps 20 --warmup 5 ;;
     bench_ddp)
       run bench_ddp 420 env ${DDP_ENV:-MXK_NOP=1} python3 bench.py --mode ddp \
         --steps "${DDP_STEPS:-10}" --warmup 3 ;;
@@ -92,7 +92,7 @@ for step in "$@"; do
     ddp_l2)
       run ddp_l2 300 python3 -u bench.py --mode ddp --layers 2 --steps "${DDP_STEPS:-3}" --warmup 1 ${DDP_ARGS:-} ;;
     validator_gloo2)
-      run validator_gloo2 400 env MXK_BENCH_BACKEND=gloo python3 -u bench.py --gpus 2 --steps 10 \
+      run validator_gloo2 400 env MXK_BENCH_BACKEND=gloo python3 -u bench.py --full --gpus 2 --steps 10 \
         --warmup 2 --allreduce-sizes 1,16,256 --ab-sizes "" ;;
     *)
       echo "unknown step $step"; exit 2 ;;

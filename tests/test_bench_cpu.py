@@ -12,13 +12,13 @@ import pytest
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run_bench(*extra, timeout=240):
+def _run_bench(*extra, timeout=240, full=True):
     env = dict(os.environ, MXK_BENCH_DEVICE="cpu", OMP_NUM_THREADS="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "TORCHELASTIC_RUN_ID"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--size", "256", "--steps", "3",
            "--warmup", "1", "--warmup-s", "0", "--allreduce-sizes", "1,2", "--allreduce-mib", "2",
-           "--ab-rounds", "2", "--ab-sizes", "128", *extra]
+           "--ab-rounds", "2", "--ab-sizes", "128", *(["--full"] if full else []), *extra]
     p = subprocess.run(cmd, env=env, cwd=REPO, capture_output=True, text=True, timeout=timeout)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -59,6 +59,48 @@ def test_bench_single_rank_contract():
     _check_contract(out, 1)
     assert out["allreduce"]["busbw_GBps"] == 0.0 and out["allreduce"]["algbw_GBps"] is None
     assert out["allreduce"]["busbw_peak_GBps"] is None
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """Without --full: the headline fields only (everything behind --full is
+    null), and --dump-outputs writes the last timed launch's output, the same
+    from run to run."""
+    import numpy as np
+    outs = []
+    for name in ("a", "b"):
+        out = _run_bench("--dump-outputs", str(tmp_path / name), full=False)
+        assert out["full"] is False and out["steps"] == 3 and out["warmup"] == 1
+        assert out["unit"] == "TFLOPS" and out["dtype"] == "bf16" and out["higher_is_better"] is True
+        expect = 2.0 * 256 ** 3 / (out["ms_per_step"] * 1e-3) / 1e12
+        assert out["value"] == pytest.approx(expect, rel=0.02, abs=0.011)
+        for moved in ("gemm_check", "hipblaslt_ab", "allreduce", "event_median_ms"):
+            assert out[moved] is None, moved
+        assert out["ab_other_sizes"] == []
+        assert out["outputs"]["file"] == "gemm_out_rank0.npy"
+        assert sorted(os.listdir(tmp_path / name)) == ["gemm_out_rank0.npy"]
+        outs.append(np.load(tmp_path / name / "gemm_out_rank0.npy"))
+    assert outs[0].dtype == np.float32 and outs[0].shape == (256, 256)
+    assert np.isfinite(outs[0]).all() and np.abs(outs[0]).max() > 1.0
+    assert np.array_equal(outs[0], outs[1])
+
+
+def test_dump_outputs_samples_large_outputs(tmp_path):
+    """An output past the byte budget is written as a fixed seeded sample."""
+    sys.path.insert(0, REPO)
+    import numpy as np
+    import torch
+
+    import bench
+    n = bench.DUMP_BUDGET_BYTES // 4 + 1000
+    C = (torch.arange(n, dtype=torch.float32) % 251).to(torch.bfloat16)
+    info = bench.dump_output(str(tmp_path), "big", C, 2)
+    arr = np.load(tmp_path / "big.npy")
+    assert arr.dtype == np.float32 and arr.size == bench.DUMP_BUDGET_BYTES // 4 // 2 == info["elements"]
+    idx = bench.dump_sample_index(n, 2)
+    assert torch.equal(idx, bench.dump_sample_index(n, 2))        # fixed, seeded
+    assert int(idx.min()) >= 0 and int(idx.max()) < n
+    assert np.array_equal(arr, (idx % 251).numpy().astype(np.float32))
+    assert bench.dump_sample_index(1000, 8) is None               # small outputs: whole
 
 
 def test_protocol_allreduce_sizes():
@@ -111,7 +153,7 @@ def test_bench_eight_ranks_protocol_sweep():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "TORCHELASTIC_RUN_ID"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "8", "--size", "128",
-           "--steps", "2", "--warmup", "1", "--warmup-s", "0", "--no-reference",
+           "--steps", "2", "--warmup", "1", "--warmup-s", "0", "--full", "--no-reference",
            "--allreduce-max-bytes", str(64 << 10), "--allreduce-mib", "0"]
     p = subprocess.run(cmd, env=env, cwd=REPO, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-3000:]
