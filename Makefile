@@ -10,6 +10,7 @@
 #   make tools      validator binaries  bin/mx-vector-add bin/mx-gemm-bench bin/mx-allreduce-perf
 #   make test-native  host unit tests of libmxnode (ASan+UBSan build)
 #   make test-native-tsan  libmxnode re-entrancy test under ThreadSanitizer
+#   make test-attention-plan  the attention backward plan's sweep (host, ASan+UBSan build)
 #
 # Everything lands inside the repo so `gpurun` snapshots carry it to the box.
 
@@ -27,7 +28,7 @@ CXXFLAGS  := -O2 -std=c++17 -fPIC -Wall -Wextra -Wno-unused-parameter -Inative/l
 LDLIBS_NODE := -ldl -lpthread
 
 KERNEL_SRCS := native/kernels/gemm_bf16.hip native/kernels/vector_add.hip \
-               native/kernels/fused_ops.hip native/kernels/optim.hip native/kernels/attention.hip native/kernels/attention_bwd256.hip native/kernels/attention_fwd256.hip native/kernels/attention_dq256.hip \
+               native/kernels/fused_ops.hip native/kernels/optim.hip native/kernels/attention_fwd.hip native/kernels/attention_bwd.hip native/kernels/attention_bwd256.hip native/kernels/attention_fwd256.hip native/kernels/attention_dq256.hip \
                native/kernels/gemm_bf16_layouts.hip native/kernels/xent.hip native/kernels/contention.hip
 KERNEL_OBJS := $(patsubst native/kernels/%.hip,$(BUILD)/kernels/%.o,$(KERNEL_SRCS))
 EXP_SRCS    := $(KERNEL_SRCS) $(wildcard native/kernels/experiments/*.hip)
@@ -38,7 +39,7 @@ NODE_SRCS := $(wildcard native/libmxnode/*.cc)
 NODE_OBJS := $(patsubst native/libmxnode/%.cc,$(BUILD)/node/%.o,$(NODE_SRCS))
 NODE_HDRS := $(wildcard native/libmxnode/*.h)
 
-.PHONY: all kernels gemm-exp node tools clean test-native test-native-tsan fake-amdsmi
+.PHONY: all kernels gemm-exp node tools clean test-native test-native-tsan test-attention-plan fake-amdsmi
 all: kernels node tools fake-amdsmi
 
 kernels: $(OUT_LIB)/libmxkernels.so
@@ -131,6 +132,14 @@ $(BUILD)/tsan/test_mxnode_threads: native/libmxnode/tests/test_mxnode_threads.cc
 	@mkdir -p $(dir $@)
 	$(CXX) $(CXXFLAGS) -g -fsanitize=thread -o $@ \
 	    native/libmxnode/tests/test_mxnode_threads.cc $(NODE_SRCS) $(LDLIBS_NODE)
+
+test-attention-plan: $(BUILD)/asan/attention_plan_sweep
+	$<
+
+$(BUILD)/asan/attention_plan_sweep: native/kernels/tests/attention_plan_sweep.cc native/kernels/attention_plan.h
+	@mkdir -p $(dir $@)
+	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -Wshadow -fsanitize=address,undefined -fno-sanitize-recover=all \
+	    -fno-omit-frame-pointer -Inative/kernels -o $@ $<
 
 clean:
 	rm -rf $(BUILD) $(OUT_LIB)/*.so $(OUT_BIN)

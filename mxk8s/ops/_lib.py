@@ -80,10 +80,8 @@ _SIGNATURES = {
     "mxk_grad_clip_scale": (_i, [_vp, _l, _vp, _f, _f, _vp, _vp]),
     "mxk_grad_sumsq": (_i, [_vp, _l, _vp, _vp, _vp]),
     "mxk_clip_scale_from_sumsq": (_i, [_vp, _f, _f, _vp, _vp]),
-    "mxk_attn_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _l, _l, _l, _f, _i, _vp]),
     "mxk_attn_fwd_variant": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _l, _l, _l, _f, _i, _i,
                                   _vp]),
-    "mxk_attn_bwd_workspace": (_l, [_i, _i, _i]),
     "mxk_attn_bwd_workspace_variant": (_l, [_i, _i, _i, _i]),
     "mxk_attn_bwd_dq256": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _l, _l, _l,
                                 _f, _i, _vp]),
@@ -96,8 +94,8 @@ _SIGNATURES = {
     "mxk_gemm_bf16_rope": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp]),
     "mxk_attn_bwd_rope": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i,
                                _l, _l, _l, _l, _l, _l, _vp, _vp, _f, _i, _vp]),
-    "mxk_attn_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i,
-                          _l, _l, _l, _l, _l, _f, _i, _vp]),
+    "mxk_attn_bwd_plan": (_i, [_i, _i, _i, _i, _l, _l, _l, _l, _l, _i, _i,
+                               ctypes.POINTER(ctypes.c_long)]),
     "mxk_xent_fwd": (_i, [_vp, _vp, _vp, _vp, _l, _i, _l, _vp]),
     "mxk_xent_bwd": (_i, [_vp, _vp, _vp, _vp, _l, _i, _l, _vp]),
     "mxk_adamw_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _f, _f, _f, _f, _f, _i, _vp, _vp]),

@@ -1,5 +1,6 @@
 """Flash attention on the hand-written gfx950 kernels
-(``native/kernels/attention.hip``).
+(``native/kernels/attention_fwd.hip``, ``attention_bwd.hip`` and the
+``attention_*256.hip`` kernels their dispatchers call).
 
 ``flash_attention(q, k, v, causal=True)`` takes q [B, S, Hq, 128] and k/v
 [B, S, Hkv, 128] bf16 tensors whose last two dims are contiguous (token
@@ -85,34 +86,9 @@ def attn_bwd(q, k, v, o, lse, dout, causal: bool = True, scale: float | None = N
 
     ``dk``/``dv`` may be preallocated views (e.g. slices of a fused dQKV
     buffer) with a token stride; by default they are fresh contiguous tensors.
-    ``variant`` 9 (default; Hq / Hkv a multiple of 4 and S % 256 == 0, else
-    6): dQ by workgroups of the 4 query heads of a GQA quad x 64 rows, one
-    wave per SIMD (attention_dq256.hip: Q / dO resident as MFMA operands in
-    the accumulator file, K / V by LDS-DMA shared by the four heads, dO / O /
-    Q staged through LDS, the delta pass folded in), then variant 6's
-    256-key dK / dV: bit-identical to variant 6 and 1-3 % faster per
-    Llama-3-8B layer at B 8 (1.02-1.04 vs 1.045-1.057 ms,
-    profiles/r6_dq256/SUMMARY.md).
-    6: variant 5's dQ kernel (it
-    also writes the row constants -lse/scale and -delta), then dK / dV by the
-    256-key workgroups of attention_bwd256.hip (one wave per SIMD, dK^T / dV^T
-    in accumulators, S / dP of both key tiles from one read of each Q / dO
-    fragment, a key tile's softmax and dK / dV pipelined into the next step):
-    1.018 vs 1.044 ms for variant 5 per Llama-3-8B layer at B 8, deterministic
-    (profiles/r5_attention/).  8: one pass, dQ added by packed-bf16 atomics
-    from the 256-key workgroups (0.983 ms; dQ summed in bf16 in a
-    nondeterministic order); 7: the same with fp32 atomics and a convert pass
-    (1.139 ms).  5: variant 3 with the delta pass (dO . O per query
-    row) folded into the dQ kernel, which then runs before dK/dV: no separate
-    delta kernel, 1.042 vs 1.064 ms per Llama-3-8B layer at B 8
-    (profiles/r4_final/attention_b8.log).  3: variant 2 with explicitly software-pipelined
-    dK/dV and dQ bodies (LDS operands read a group ahead instead of one
-    lgkmcnt(0) per MFMA), bit-identical to 2 and 15 % faster (1.070 vs 1.262
-    ms per Llama-3-8B layer at B 8: profiles/r2_attention/); 2: dK/dV
-    accumulated over the query-head group in one workgroup, bf16 out, K/V and
-    Q/dO tiles by LDS-DMA (1.21 vs 1.31-1.36 ms, profiles/r1_attention/);
-    1: the same with register-staged tiles; 0: per-query-head fp32 partials
-    + GQA reduce."""
+    ``variant`` 0-9, default 9: the variants, their history and how a layout
+    one does not take degrades (9 -> 6 -> 5) are listed beside ``AttnBwdPlan``
+    in ``native/kernels/attention_plan.h``."""
     B, S, Hq, D = q.shape
     Hkv = k.shape[2]
     variant = _BWD_VARIANT if variant is None else variant
@@ -162,14 +138,28 @@ class _FlashAttention(torch.autograd.Function):
 _FUSED_ROPE_BWD = os.environ.get("MXK_FUSED_ROPE_BWD", "1") != "0"
 
 
+def _split_qkv(qkv, hq: int, hkv: int, hd: int):
+    """q [B,S,hq,hd], k and v [B,S,hkv,hd] as views of a fused [B, S, (hq + 2 hkv) hd] buffer."""
+    B, S, _ = qkv.shape
+    return (qkv[..., :hq * hd].view(B, S, hq, hd),
+            qkv[..., hq * hd:(hq + hkv) * hd].view(B, S, hkv, hd),
+            qkv[..., (hq + hkv) * hd:].view(B, S, hkv, hd))
+
+
+def _fused_node_layout(S: int, hq: int, hkv: int, hd: int, cos) -> bool:
+    """Heads and sequence lengths the fused RoPE nodes take (what backward
+    variant 9 takes: GQA quads, S % 256), with rotary tables that cover S."""
+    return (hd == HEAD_DIM and hkv > 0 and hq % hkv == 0 and (hq // hkv) % 4 == 0
+            and S % 256 == 0 and cos.shape[0] >= S)
+
+
 class _QKVRoPEAttention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv, cos, sin, hq: int, hkv: int, hd: int, causal: bool, scale):
         from .fused import _rope_launch
-        B, S, _ = qkv.shape
-        q = _rope_launch(qkv[..., :hq * hd].view(B, S, hq, hd), cos, sin, 1.0)
-        k = _rope_launch(qkv[..., hq * hd:(hq + hkv) * hd].view(B, S, hkv, hd), cos, sin, 1.0)
-        v = qkv[..., (hq + hkv) * hd:].view(B, S, hkv, hd)
+        q, k, v = _split_qkv(qkv, hq, hkv, hd)
+        q = _rope_launch(q, cos, sin, 1.0)
+        k = _rope_launch(k, cos, sin, 1.0)
         o, lse = attn_fwd(q, k, v, causal=causal, scale=scale)
         ctx.save_for_backward(q, k, v, o, lse, cos, sin)
         ctx.causal, ctx.scale, ctx.dims = causal, scale, (hq, hkv, hd)
@@ -190,9 +180,7 @@ def _rope_attn_backward(q, k, v, o, lse, cos, sin, dout, dims, causal, scale):
     B, S = q.shape[:2]
     scale = scale if scale is not None else 1.0 / math.sqrt(hd)
     dqkv = torch.empty((B, S, (hq + 2 * hkv) * hd), dtype=q.dtype, device=q.device)
-    dq = dqkv[..., :hq * hd].view(B, S, hq, hd)
-    dk = dqkv[..., hq * hd:(hq + hkv) * hd].view(B, S, hkv, hd)
-    dv = dqkv[..., (hq + hkv) * hd:].view(B, S, hkv, hd)
+    dq, dk, dv = _split_qkv(dqkv, hq, hkv, hd)
     dout = dout.contiguous()
     if _BWD_VARIANT == 9:
         L = _lib.lib()
@@ -240,9 +228,7 @@ class _ProjRoPEAttention(torch.autograd.Function):
                                            qkv.stride(0), cos.data_ptr(), sin.data_ptr(), S,
                                            (hq + hkv) * hd, _lib.stream_ptr(x.device))
         qkv = qkv.view(B, S, N)
-        q = qkv[..., :hq * hd].view(B, S, hq, hd)
-        k = qkv[..., hq * hd:(hq + hkv) * hd].view(B, S, hkv, hd)
-        v = qkv[..., (hq + hkv) * hd:].view(B, S, hkv, hd)
+        q, k, v = _split_qkv(qkv, hq, hkv, hd)
         if st != 0:
             if st != 1:
                 _lib.check(st, "mxk_gemm_bf16_rope")
@@ -273,9 +259,8 @@ def proj_rope_attention(x: torch.Tensor, weight: torch.Tensor, cos: torch.Tensor
     _ProjRoPEAttention); None when the layout is not the fused path's."""
     if not (_FUSED_ROPE_BWD and _FUSED_ROPE_FWD and x.is_cuda and x.dtype == torch.bfloat16
             and weight.dtype == torch.bfloat16 and x.dim() == 3 and weight.is_contiguous()
-            and weight.shape[0] == (hq + 2 * hkv) * hd and hd == HEAD_DIM and hkv > 0
-            and hq % hkv == 0 and (hq // hkv) % 4 == 0 and x.shape[1] % 256 == 0
-            and cos.shape[0] >= x.shape[1]):
+            and weight.shape[0] == (hq + 2 * hkv) * hd
+            and _fused_node_layout(x.shape[1], hq, hkv, hd, cos)):
         return None
     S = x.shape[1]
     return _ProjRoPEAttention.apply(x, weight, cos[:S].float().contiguous(),
@@ -295,10 +280,9 @@ def qkv_rope_attention(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, 
     layout is not the fused path's (the caller then runs qkv_rope +
     flash_attention)."""
     if not (_FUSED_ROPE_BWD and qkv.is_cuda and qkv.dtype == torch.bfloat16 and qkv.dim() == 3
-            and qkv.is_contiguous() and qkv.data_ptr() % 16 == 0 and hd == HEAD_DIM
-            and hkv > 0 and hq % hkv == 0 and (hq // hkv) % 4 == 0
-            and qkv.shape[-1] == (hq + 2 * hkv) * hd and qkv.shape[1] % 256 == 0
-            and cos.shape[0] >= qkv.shape[1]):
+            and qkv.is_contiguous() and qkv.data_ptr() % 16 == 0
+            and qkv.shape[-1] == (hq + 2 * hkv) * hd
+            and _fused_node_layout(qkv.shape[1], hq, hkv, hd, cos)):
         return None
     S = qkv.shape[1]
     return _QKVRoPEAttention.apply(qkv, cos[:S].float().contiguous(), sin[:S].float().contiguous(),

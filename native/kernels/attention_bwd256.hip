@@ -1,6 +1,6 @@
 // Flash attention backward, dK/dV with 256 keys per workgroup (gfx950).
 //
-// The round-4 PMC of the GQA dK/dV kernel (attention.hip, mxk_attn_bwd_dkdv16:
+// The round-4 PMC of the GQA dK/dV kernel (attention_bwd.hip, mxk_attn_bwd_dkdv16:
 // 8 waves x 16 keys = 128 keys per workgroup, 16x16x32 MFMAs) shows it as the
 // slowest piece of the backward: 39 % MFMA busy, 16 % of its wave cycles
 // waiting on LDS, and 857 MB per Llama-3-8B layer fetched from beyond L2
@@ -31,7 +31,7 @@
 //     vmcnt waits.
 //
 // This file computes dK and dV only; dQ comes from the query-parallel dQ
-// kernel of attention.hip (variant 5's, with the delta pass folded in),
+// kernel of attention_bwd.hip (variant 5's, with the delta pass folded in),
 // which writes the {-LSE/scale, -delta} row pairs this kernel streams.  The
 // split costs two MFMA products per tile over a single pass (S and dP are
 // recomputed) but needs no dQ atomics: at 256 keys per workgroup a single
@@ -40,7 +40,7 @@
 // floor alone is ~0.93 ms per Llama-3-8B layer (B 8, S 2048, causal) - more
 // than the whole two-kernel backward.
 //
-// Layouts as attention.hip: q [B, S, Hq, 128] (token stride q_tok), k / v
+// Layouts as attention_fwd.hip: q [B, S, Hq, 128] (token stride q_tok), k / v
 // [B, S, Hkv, 128] (k_tok / v_tok), dout [B, S, Hq, 128] contiguous, rowc
 // [B, Hq, S] x {-lse/scale, -delta} fp32, dk / dv [B, S, Hkv, 128] (token
 // strides dk_tok / dv_tok).  S % 256 == 0; every Q / K / V / dO panel must
@@ -49,7 +49,6 @@
 
 namespace {
 constexpr int KW = 64;                        // keys per wave
-constexpr int KBLK = 256;                     // keys per workgroup
 constexpr int QS = 32;                        // query rows per item
 constexpr int QIMG = QS * 256;                // 8 KiB: one 32-row slice image
 constexpr int KIMG = KBLK * 256;              // 64 KiB
@@ -738,7 +737,7 @@ mxk_attn_bwd_dkdv256_kernel(const uint16_t* __restrict__ q, const uint16_t* __re
 }
 
 // dK / dV of the 256-key kernel.  rowc: [B, Hq, S] x {-lse/scale, -delta}
-// (written by the dQ kernel of attention.hip with ROWC).  rcos / rsin
+// (written by the dQ kernel of attention_bwd.hip with ROWC).  rcos / rsin
 // (both or neither): the rotary-embedding backward fused into the dK store.
 // Returns a HIP status; hipErrorInvalidValue when a layout does not fit.
 static int dkdv256_launch(const void* q, const void* k, const void* v, const void* dout,
@@ -746,36 +745,19 @@ static int dkdv256_launch(const void* q, const void* k, const void* v, const voi
                           long q_tok, long k_tok, long v_tok, long dk_tok, long dv_tok,
                           const float* rcos, const float* rsin, float scale, int causal,
                           hipStream_t stream) {
-  if (B < 1 || S < KBLK || S % KBLK || Hkv < 1 || Hq % Hkv || q_tok % 8 || k_tok % 8 ||
-      v_tok % 8 || dk_tok % 4 || dv_tok % 4 ||
-      static_cast<long>(S) * q_tok * 2 >= (1L << 32) ||
-      static_cast<long>(S) * k_tok * 2 >= (1L << 32) ||
-      static_cast<long>(S) * Hq * D * 2 >= (1L << 32) ||
-      (reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) |
-       reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(dout) |
-       reinterpret_cast<uintptr_t>(rowc) | reinterpret_cast<uintptr_t>(rcos) |
-       reinterpret_cast<uintptr_t>(rsin)) % 16 ||
-      (reinterpret_cast<uintptr_t>(dk) | reinterpret_cast<uintptr_t>(dv)) % 8 ||
-      (rcos == nullptr) != (rsin == nullptr))
+  const AttnLayout L{B, S, Hq, Hkv, q_tok, k_tok, v_tok, 0, dk_tok, dv_tok, causal};
+  if (!attn_dkdv256_ok(L) || !attn_aligned(16, q, k, v, dout, rowc, rcos, rsin) ||
+      !attn_aligned(8, dk, dv) || (rcos == nullptr) != (rsin == nullptr))
     return static_cast<int>(hipErrorInvalidValue);
   const int nwg = B * Hkv * (S / KBLK);
-  const auto* Q = static_cast<const uint16_t*>(q);
-  const auto* K = static_cast<const uint16_t*>(k);
-  const auto* V = static_cast<const uint16_t*>(v);
-  const auto* dO = static_cast<const uint16_t*>(dout);
-  auto* dK = static_cast<uint16_t*>(dk);
-  auto* dV = static_cast<uint16_t*>(dv);
-#define MXK_DKDV256(C, R)                                                                    \
-  hipLaunchKernelGGL((mxk_attn_bwd_dkdv256_kernel<C, 0, false, R>), dim3(nwg), dim3(256), 0, \
-                     stream, Q, K, V, dO, rowc, dK, dV, S, Hq, Hkv, q_tok, k_tok, v_tok, dk_tok, \
-                     dv_tok, scale, nullptr, nullptr, rcos, rsin)
-  if (rcos) {
-    if (causal) MXK_DKDV256(true, true);
-    else MXK_DKDV256(false, true);
-  } else {
-    if (causal) MXK_DKDV256(true, false);
-    else MXK_DKDV256(false, false);
-  }
+#define MXK_DKDV256(R)                                                                          \
+  MXK_WITH_BOOL(C, causal,                                                                      \
+                hipLaunchKernelGGL((mxk_attn_bwd_dkdv256_kernel<C, 0, false, R>), dim3(nwg),    \
+                                   dim3(256), 0, stream, bf(q), bf(k), bf(v), bf(dout), rowc,   \
+                                   bf(dk), bf(dv), S, Hq, Hkv, q_tok, k_tok, v_tok, dk_tok,     \
+                                   dv_tok, scale, nullptr, nullptr, rcos, rsin))
+  if (rcos) MXK_DKDV256(true);
+  else MXK_DKDV256(false);
 #undef MXK_DKDV256
   MXK_RETURN_LAUNCH_STATUS();
 }
@@ -854,8 +836,7 @@ mxk_attn_bwd_dq_convert_kernel(const float* __restrict__ acc, uint16_t* __restri
 // Workspace bytes of the one-pass backward: rowc (8 B per row) and, for the
 // fp32 atomics, dq_acc (512 B per row).
 MXK_API long mxk_attn_bwd_onepass_workspace(int B, int S, int Hq, int bf16_atomics) {
-  const long rows = static_cast<long>(B) * Hq * S;
-  return rows * 8 + (bf16_atomics ? 0 : rows * D * 4);
+  return attn_bwd_workspace(B, S, Hq, bf16_atomics ? 8 : 7);
 }
 
 // One-pass backward: dq [B, S, Hq, 128] contiguous.  bf16_atomics 0: fp32
@@ -867,49 +848,31 @@ MXK_API int mxk_attn_bwd_onepass(const void* q, const void* k, const void* v, co
                                  void* workspace, int B, int S, int Hq, int Hkv, long q_tok,
                                  long k_tok, long v_tok, long dk_tok, long dv_tok, float scale,
                                  int causal, int bf16_atomics, hipStream_t stream) {
-  if (B < 1 || S < KBLK || S % KBLK || Hkv < 1 || Hq % Hkv || q_tok % 8 || k_tok % 8 ||
-      v_tok % 8 || dk_tok % 4 || dv_tok % 4 ||
-      static_cast<long>(S) * q_tok * 2 >= (1L << 32) ||
-      static_cast<long>(S) * k_tok * 2 >= (1L << 32) ||
-      static_cast<long>(S) * Hq * D * 2 >= (1L << 32) ||
-      (reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) |
-       reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(o) |
-       reinterpret_cast<uintptr_t>(dout) | reinterpret_cast<uintptr_t>(dq) |
-       reinterpret_cast<uintptr_t>(workspace)) % 16 ||
-      (reinterpret_cast<uintptr_t>(dk) | reinterpret_cast<uintptr_t>(dv)) % 8)
+  const AttnLayout L{B, S, Hq, Hkv, q_tok, k_tok, v_tok, 0, dk_tok, dv_tok, causal};
+  if (!attn_dkdv256_ok(L) || !attn_aligned(16, q, k, v, o, dout, dq, workspace) ||
+      !attn_aligned(8, dk, dv))
     return static_cast<int>(hipErrorInvalidValue);
   const long rows = static_cast<long>(B) * Hq * S;
   float* rowc = static_cast<float*>(workspace);
   float* dq_acc = rowc + 2 * rows;
-  const auto* O = static_cast<const uint16_t*>(o);
-  const auto* dO = static_cast<const uint16_t*>(dout);
   const unsigned pblocks = static_cast<unsigned>((rows * 16 + 255) / 256);
-  if (bf16_atomics)
-    hipLaunchKernelGGL(mxk_attn_bwd_prep_kernel<2>, dim3(pblocks), dim3(256), 0, stream, O, dO, lse,
-                       rowc, dq, S, Hq, rows, 1.f / scale);
-  else
-    hipLaunchKernelGGL(mxk_attn_bwd_prep_kernel<1>, dim3(pblocks), dim3(256), 0, stream, O, dO, lse,
-                       rowc, static_cast<void*>(dq_acc), S, Hq, rows, 1.f / scale);
-  const int nwg = B * Hkv * (S / KBLK);
-  const auto* Q = static_cast<const uint16_t*>(q);
-  const auto* K = static_cast<const uint16_t*>(k);
-  const auto* V = static_cast<const uint16_t*>(v);
-  auto* dK = static_cast<uint16_t*>(dk);
-  auto* dV = static_cast<uint16_t*>(dv);
   void* dqo = bf16_atomics ? dq : static_cast<void*>(dq_acc);
-#define MXK_ONEPASS_LAUNCH(C, M)                                                                  \
-  hipLaunchKernelGGL((mxk_attn_bwd_dkdv256_kernel<C, M>), dim3(nwg), dim3(256), 0, stream, Q, K,   \
-                     V, dO, rowc, dK, dV, S, Hq, Hkv, q_tok, k_tok, v_tok, dk_tok, dv_tok, scale, \
-                     dqo)
-  if (causal && bf16_atomics) MXK_ONEPASS_LAUNCH(true, 2);
-  else if (causal) MXK_ONEPASS_LAUNCH(true, 1);
-  else if (bf16_atomics) MXK_ONEPASS_LAUNCH(false, 2);
-  else MXK_ONEPASS_LAUNCH(false, 1);
-#undef MXK_ONEPASS_LAUNCH
+  // ZERO / DQ mode 2: packed bf16 atomics into dq, 1: fp32 atomics into dq_acc
+  MXK_WITH_BOOL(BF, bf16_atomics,
+                hipLaunchKernelGGL(mxk_attn_bwd_prep_kernel<BF ? 2 : 1>, dim3(pblocks), dim3(256), 0,
+                                   stream, bf(o), bf(dout), lse, rowc, dqo, S, Hq, rows,
+                                   1.f / scale));
+  const int nwg = B * Hkv * (S / KBLK);
+  MXK_WITH_BOOL(BF, bf16_atomics,
+                MXK_WITH_BOOL(C, causal,
+                              hipLaunchKernelGGL((mxk_attn_bwd_dkdv256_kernel<C, BF ? 2 : 1>),
+                                                 dim3(nwg), dim3(256), 0, stream, bf(q), bf(k),
+                                                 bf(v), bf(dout), rowc, bf(dk), bf(dv), S, Hq, Hkv,
+                                                 q_tok, k_tok, v_tok, dk_tok, dv_tok, scale, dqo)));
   if (!bf16_atomics) {
     const long n8 = rows * D / 8;
     hipLaunchKernelGGL(mxk_attn_bwd_dq_convert_kernel, dim3(static_cast<unsigned>((n8 + 255) / 256)),
-                       dim3(256), 0, stream, dq_acc, static_cast<uint16_t*>(dq), n8, scale);
+                       dim3(256), 0, stream, dq_acc, bf(dq), n8, scale);
   }
   MXK_RETURN_LAUNCH_STATUS();
 }
@@ -926,19 +889,10 @@ MXK_API int mxk_attn_bwd_dkdv256_stamps(const void* q, const void* k, const void
   if (B < 1 || S < KBLK || S % KBLK || Hkv < 1 || Hq % Hkv || !stamps)
     return static_cast<int>(hipErrorInvalidValue);
   const int nwg = B * Hkv * (S / KBLK);
-  const auto* Q = static_cast<const uint16_t*>(q);
-  const auto* K = static_cast<const uint16_t*>(k);
-  const auto* V = static_cast<const uint16_t*>(v);
-  const auto* dO = static_cast<const uint16_t*>(dout);
-  auto* dK = static_cast<uint16_t*>(dk);
-  auto* dV = static_cast<uint16_t*>(dv);
-  if (causal)
-    hipLaunchKernelGGL((mxk_attn_bwd_dkdv256_kernel<true, 0, true>), dim3(nwg), dim3(256), 0,
-                       stream, Q, K, V, dO, rowc, dK, dV, S, Hq, Hkv, q_tok, k_tok, v_tok, dk_tok,
-                       dv_tok, scale, nullptr, stamps);
-  else
-    hipLaunchKernelGGL((mxk_attn_bwd_dkdv256_kernel<false, 0, true>), dim3(nwg), dim3(256), 0,
-                       stream, Q, K, V, dO, rowc, dK, dV, S, Hq, Hkv, q_tok, k_tok, v_tok, dk_tok,
-                       dv_tok, scale, nullptr, stamps);
+  MXK_WITH_BOOL(C, causal,
+                hipLaunchKernelGGL((mxk_attn_bwd_dkdv256_kernel<C, 0, true>), dim3(nwg), dim3(256),
+                                   0, stream, bf(q), bf(k), bf(v), bf(dout), rowc, bf(dk), bf(dv),
+                                   S, Hq, Hkv, q_tok, k_tok, v_tok, dk_tok, dv_tok, scale, nullptr,
+                                   stamps));
   MXK_RETURN_LAUNCH_STATUS();
 }

@@ -1,7 +1,7 @@
 // Flash attention backward, dQ with one wave per SIMD (gfx950; backward
 // variant 9).
 //
-// The dQ kernel of variants 5 / 6 (attention.hip, mxk_attn_bwd_dq_kernel:
+// The dQ kernel of variants 5 / 6 (attention_bwd.hip, mxk_attn_bwd_dq_kernel:
 // 4 waves x 32 query rows, two workgroups per CU) takes 459.5 us of the
 // 1.018 ms Llama-3-8B layer backward at 44.8 % MFMA busy and 81.9 % L2 hit
 // (profiles/r5_attention/pmc_default_fwd4_bwd6_and_v8.txt): every K / V
@@ -35,14 +35,13 @@
 // that the 256-key dK / dV kernel streams, so variant 9 is this kernel then
 // mxk_attn_bwd_dkdv256 - deterministic, no atomics.
 //
-// Layouts as attention.hip: q [B, S, Hq, 128] (token stride q_tok), k / v
+// Layouts as attention_fwd.hip: q [B, S, Hq, 128] (token stride q_tok), k / v
 // [B, S, Hkv, 128] (k_tok / v_tok), o / dout / dq [B, S, Hq, 128] contiguous,
 // lse [B, Hq, S] fp32 (natural log), rowc [B, Hq, S] x float2.  Hq / Hkv a
 // multiple of 4, S % 64 == 0, K / V panels within a 32-bit buffer range.
 #include "attention_common.h"
 
 namespace {
-constexpr int QW = 64;                     // query rows per wave (and workgroup)
 constexpr int KT = 64;                     // keys per DMA tile (two steps of 32)
 constexpr int QSLOT = 2 * TILE_BYTES;      // K | V image of one tile (32 KiB)
 constexpr int QNSLOT = 4;
@@ -698,28 +697,15 @@ MXK_API int mxk_attn_bwd_dq256(const void* q, const void* k, const void* v, cons
                                const void* dout, const float* lse, void* dq, float* rowc, int B,
                                int S, int Hq, int Hkv, long q_tok, long k_tok, long v_tok,
                                float scale, int causal, hipStream_t stream) {
-  if (B < 1 || S < QW || S % QW || Hkv < 1 || Hq % Hkv || (Hq / Hkv) % 4 || q_tok % 8 ||
-      k_tok % 8 || v_tok % 8 || static_cast<long>(S) * k_tok * 2 >= (1L << 32) ||
-      static_cast<long>(S) * v_tok * 2 >= (1L << 32) ||
-      (reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) |
-       reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(o) |
-       reinterpret_cast<uintptr_t>(dout) | reinterpret_cast<uintptr_t>(dq) |
-       reinterpret_cast<uintptr_t>(rowc)) % 16)
+  const AttnLayout L{B, S, Hq, Hkv, q_tok, k_tok, v_tok, static_cast<long>(Hq) * D, 0, 0, causal};
+  if (!attn_dq256_ok(L) || !attn_aligned(16, q, k, v, o, dout, dq, rowc))
     return static_cast<int>(hipErrorInvalidValue);
   const int nwg = B * (Hq / 4) * (S / QW);
-  const auto* Q = static_cast<const uint16_t*>(q);
-  const auto* K = static_cast<const uint16_t*>(k);
-  const auto* V = static_cast<const uint16_t*>(v);
-  const auto* O = static_cast<const uint16_t*>(o);
-  const auto* dO = static_cast<const uint16_t*>(dout);
-  auto* dQ = static_cast<uint16_t*>(dq);
   const int succ = dq256_succ();
-  if (causal)
-    hipLaunchKernelGGL(mxk_attn_bwd_dq256_kernel<true>, dim3(nwg), dim3(256), 0, stream, Q, K, V, O,
-                       dO, lse, dQ, rowc, S, Hq, Hkv, q_tok, k_tok, v_tok, scale, nullptr, succ);
-  else
-    hipLaunchKernelGGL(mxk_attn_bwd_dq256_kernel<false>, dim3(nwg), dim3(256), 0, stream, Q, K, V,
-                       O, dO, lse, dQ, rowc, S, Hq, Hkv, q_tok, k_tok, v_tok, scale, nullptr, succ);
+  MXK_WITH_BOOL(C, causal,
+                hipLaunchKernelGGL(mxk_attn_bwd_dq256_kernel<C>, dim3(nwg), dim3(256), 0, stream,
+                                   bf(q), bf(k), bf(v), bf(o), bf(dout), lse, bf(dq), rowc, S, Hq,
+                                   Hkv, q_tok, k_tok, v_tok, scale, nullptr, succ));
   MXK_RETURN_LAUNCH_STATUS();
 }
 
@@ -730,32 +716,17 @@ MXK_API int mxk_attn_bwd_dq256_rope(const void* q, const void* k, const void* v,
                                     int B, int S, int Hq, int Hkv, long q_tok, long k_tok,
                                     long v_tok, long dq_tok, const float* rcos, const float* rsin,
                                     float scale, int causal, hipStream_t stream) {
-  if (B < 1 || S < QW || S % QW || Hkv < 1 || Hq % Hkv || (Hq / Hkv) % 4 || q_tok % 8 ||
-      k_tok % 8 || v_tok % 8 || dq_tok < static_cast<long>(Hq) * D || dq_tok % 8 || !rcos ||
-      !rsin || static_cast<long>(S) * k_tok * 2 >= (1L << 32) ||
-      static_cast<long>(S) * v_tok * 2 >= (1L << 32) ||
-      (reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) |
-       reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(o) |
-       reinterpret_cast<uintptr_t>(dout) | reinterpret_cast<uintptr_t>(dq) |
-       reinterpret_cast<uintptr_t>(rowc) | reinterpret_cast<uintptr_t>(rcos) |
-       reinterpret_cast<uintptr_t>(rsin)) % 16)
+  const AttnLayout L{B, S, Hq, Hkv, q_tok, k_tok, v_tok, dq_tok, 0, 0, causal};
+  if (!attn_dq256_rope_ok(L) || !rcos || !rsin ||
+      !attn_aligned(16, q, k, v, o, dout, dq, rowc, rcos, rsin))
     return static_cast<int>(hipErrorInvalidValue);
   const int nwg = B * (Hq / 4) * (S / QW);
-  const auto* Q = static_cast<const uint16_t*>(q);
-  const auto* K = static_cast<const uint16_t*>(k);
-  const auto* V = static_cast<const uint16_t*>(v);
-  const auto* O = static_cast<const uint16_t*>(o);
-  const auto* dO = static_cast<const uint16_t*>(dout);
-  auto* dQ = static_cast<uint16_t*>(dq);
   const int succ = dq256_succ();
-  if (causal)
-    hipLaunchKernelGGL((mxk_attn_bwd_dq256_kernel<true, 0, false, true>), dim3(nwg), dim3(256), 0,
-                       stream, Q, K, V, O, dO, lse, dQ, rowc, S, Hq, Hkv, q_tok, k_tok, v_tok, scale,
-                       nullptr, succ, dq_tok, rcos, rsin);
-  else
-    hipLaunchKernelGGL((mxk_attn_bwd_dq256_kernel<false, 0, false, true>), dim3(nwg), dim3(256), 0,
-                       stream, Q, K, V, O, dO, lse, dQ, rowc, S, Hq, Hkv, q_tok, k_tok, v_tok, scale,
-                       nullptr, succ, dq_tok, rcos, rsin);
+  MXK_WITH_BOOL(C, causal,
+                hipLaunchKernelGGL((mxk_attn_bwd_dq256_kernel<C, 0, false, true>), dim3(nwg),
+                                   dim3(256), 0, stream, bf(q), bf(k), bf(v), bf(o), bf(dout), lse,
+                                   bf(dq), rowc, S, Hq, Hkv, q_tok, k_tok, v_tok, scale, nullptr,
+                                   succ, dq_tok, rcos, rsin));
   MXK_RETURN_LAUNCH_STATUS();
 }
 
@@ -768,15 +739,10 @@ MXK_API int mxk_attn_bwd_dq256_dbg(const void* q, const void* k, const void* v, 
   if (B < 1 || S < QW || S % QW || Hkv < 1 || Hq % Hkv || (Hq / Hkv) % 4 || dbg < 1 || dbg > 3)
     return static_cast<int>(hipErrorInvalidValue);
   const int nwg = B * (Hq / 4) * (S / QW);
-  const auto* Q = static_cast<const uint16_t*>(q);
-  const auto* K = static_cast<const uint16_t*>(k);
-  const auto* V = static_cast<const uint16_t*>(v);
-  const auto* O = static_cast<const uint16_t*>(o);
-  const auto* dO = static_cast<const uint16_t*>(dout);
-  auto* dQ = static_cast<uint16_t*>(dq);
 #define MXK_DQ256_DBG(N)                                                                         \
-  hipLaunchKernelGGL((mxk_attn_bwd_dq256_kernel<false, N>), dim3(nwg), dim3(256), 0, stream, Q, K, \
-                     V, O, dO, lse, dQ, rowc, S, Hq, Hkv, q_tok, k_tok, v_tok, scale)
+  hipLaunchKernelGGL((mxk_attn_bwd_dq256_kernel<false, N>), dim3(nwg), dim3(256), 0, stream,      \
+                     bf(q), bf(k), bf(v), bf(o), bf(dout), lse, bf(dq), rowc, S, Hq, Hkv, q_tok, \
+                     k_tok, v_tok, scale)
   if (dbg == 1) MXK_DQ256_DBG(1);
   else if (dbg == 2) MXK_DQ256_DBG(2);
   else MXK_DQ256_DBG(3);
@@ -796,9 +762,7 @@ MXK_API int mxk_attn_bwd_dq256_stamps(const void* q, const void* k, const void* 
     return static_cast<int>(hipErrorInvalidValue);
   const int nwg = B * (Hq / 4) * (S / QW);
   hipLaunchKernelGGL((mxk_attn_bwd_dq256_kernel<true, 0, true>), dim3(nwg), dim3(256), 0, stream,
-                     static_cast<const uint16_t*>(q), static_cast<const uint16_t*>(k),
-                     static_cast<const uint16_t*>(v), static_cast<const uint16_t*>(o),
-                     static_cast<const uint16_t*>(dout), lse, static_cast<uint16_t*>(dq), rowc, S,
-                     Hq, Hkv, q_tok, k_tok, v_tok, scale, stamps, dq256_succ());
+                     bf(q), bf(k), bf(v), bf(o), bf(dout), lse, bf(dq), rowc, S, Hq, Hkv, q_tok,
+                     k_tok, v_tok, scale, stamps, dq256_succ());
   MXK_RETURN_LAUNCH_STATUS();
 }

@@ -1,7 +1,7 @@
 // Flash attention forward, one wave per SIMD with two 32-row groups per wave
 // (gfx950; forward variant 10).
 //
-// The default forward (attention.hip variant 4: 4 waves x 32 rows, two
+// The default forward (attention_fwd.hip variant 4: 4 waves x 32 rows, two
 // workgroups per CU) keeps the matrix cores 45 % busy: each wave runs its
 // QK^T MFMAs, then its softmax, then its PV MFMAs, and only the other wave
 // of the SIMD can fill the gaps (profiles/r4_attention/pmc_fwd4_bwd5.txt).
@@ -26,20 +26,19 @@
 // Registers: O^T of both groups (2 x 4 x 16) in AGPRs, pinned by inline-asm
 // MFMAs; S^T of both groups (2 x 2 x 16) in VGPRs, also asm MFMAs (the VALU
 // reads them), with explicit XDL-write -> VALU-read wait states; Q in VGPRs.
-// Swapped QK^T as in attention.hip: the query is the MFMA lane, so the row
+// Swapped QK^T as in attention_fwd.hip: the query is the MFMA lane, so the row
 // statistics are per lane and P^T leaves the accumulator as the B operand of
 // O^T += V^T P^T with V^T by ds_read_b64_tr_b16 from the row-major V image.
 // K / V tiles by LDS-DMA into a 4-slot ring (two tiles of lead), one barrier
 // per tile.  Causal: every wave walks every tile of its block (a wave past
 // its diagonal sees only masked keys) - no divergent control flow.
 //
-// Layouts as attention.hip: q [B, S, Hq, 128] (token stride q_tok), k / v
+// Layouts as attention_fwd.hip: q [B, S, Hq, 128] (token stride q_tok), k / v
 // [B, S, Hkv, 128] (k_tok / v_tok), o [B, S, Hq, 128] contiguous, lse
 // [B, Hq, S] fp32 (natural log).  S % 256 == 0.
 #include "attention_common.h"
 
 namespace {
-constexpr int QB = 256;                        // query rows per workgroup
 constexpr int KT = 64;                         // keys per tile
 constexpr int FSLOT = 2 * TILE_BYTES;          // K | V image of one tile (32 KiB)
 constexpr int FNSLOT = 4;
@@ -522,27 +521,18 @@ mxk_attn_fwd256_kernel(const uint16_t* __restrict__ q, const uint16_t* __restric
 }
 
 // Forward variant 10.  Returns hipErrorInvalidValue for layouts it does not
-// take (S % 256, 32-bit buffer offsets); attention.hip then falls back.
+// take (S % 256, 32-bit buffer offsets: attn_fwd256_ok); mxk_attn_fwd_variant
+// then runs variant 4.
 MXK_API int mxk_attn_fwd256(const void* q, const void* k, const void* v, void* o, float* lse,
                             int B, int S, int Hq, int Hkv, long q_tok, long k_tok, long v_tok,
                             float scale, int causal, hipStream_t stream) {
-  if (B < 1 || S < QB || S % QB || Hkv < 1 || Hq % Hkv || q_tok % 8 || k_tok % 8 || v_tok % 8 ||
-      static_cast<long>(S) * k_tok * 2 >= (1L << 32) ||
-      static_cast<long>(S) * v_tok * 2 >= (1L << 32) ||
-      (reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) |
-       reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(o)) % 16)
+  const AttnLayout L{B, S, Hq, Hkv, q_tok, k_tok, v_tok, 0, 0, 0, causal};
+  if (!attn_fwd256_ok(L) || !attn_aligned(16, q, k, v, o))
     return static_cast<int>(hipErrorInvalidValue);
   const int nwg = B * Hq * (S / QB);
-  const auto* Q = static_cast<const uint16_t*>(q);
-  const auto* K = static_cast<const uint16_t*>(k);
-  const auto* V = static_cast<const uint16_t*>(v);
-  auto* O = static_cast<uint16_t*>(o);
-  if (causal)
-    hipLaunchKernelGGL(mxk_attn_fwd256_kernel<true>, dim3(nwg), dim3(256), 0, stream, Q, K, V, O,
-                       lse, S, Hq, Hkv, q_tok, k_tok, v_tok, scale);
-  else
-    hipLaunchKernelGGL(mxk_attn_fwd256_kernel<false>, dim3(nwg), dim3(256), 0, stream, Q, K, V, O,
-                       lse, S, Hq, Hkv, q_tok, k_tok, v_tok, scale);
+  MXK_WITH_BOOL(C, causal,
+                hipLaunchKernelGGL(mxk_attn_fwd256_kernel<C>, dim3(nwg), dim3(256), 0, stream, bf(q),
+                                   bf(k), bf(v), bf(o), lse, S, Hq, Hkv, q_tok, k_tok, v_tok, scale));
   MXK_RETURN_LAUNCH_STATUS();
 }
 
@@ -558,15 +548,9 @@ MXK_API int mxk_attn_fwd256_stamps(const void* q, const void* k, const void* v, 
       !stamps)
     return static_cast<int>(hipErrorInvalidValue);
   const int nwg = B * Hq * (S / QB);
-  const auto* Q = static_cast<const uint16_t*>(q);
-  const auto* K = static_cast<const uint16_t*>(k);
-  const auto* V = static_cast<const uint16_t*>(v);
-  auto* O = static_cast<uint16_t*>(o);
-  if (causal)
-    hipLaunchKernelGGL((mxk_attn_fwd256_kernel<true, true>), dim3(nwg), dim3(256), 0, stream, Q, K,
-                       V, O, lse, S, Hq, Hkv, q_tok, k_tok, v_tok, scale, stamps);
-  else
-    hipLaunchKernelGGL((mxk_attn_fwd256_kernel<false, true>), dim3(nwg), dim3(256), 0, stream, Q,
-                       K, V, O, lse, S, Hq, Hkv, q_tok, k_tok, v_tok, scale, stamps);
+  MXK_WITH_BOOL(C, causal,
+                hipLaunchKernelGGL((mxk_attn_fwd256_kernel<C, true>), dim3(nwg), dim3(256), 0,
+                                   stream, bf(q), bf(k), bf(v), bf(o), lse, S, Hq, Hkv, q_tok,
+                                   k_tok, v_tok, scale, stamps));
   MXK_RETURN_LAUNCH_STATUS();
 }

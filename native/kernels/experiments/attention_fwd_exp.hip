@@ -1,6 +1,6 @@
 // Flash-attention forward A/B records (variants 5-9), built only into the
 // experiments library (`make gemm-exp` -> libmxkernels_exp.so, selected with
-// MXK_KERNELS_LIB); mxk_attn_fwd_variant (attention.hip) dispatches here in that
+// MXK_KERNELS_LIB); mxk_attn_fwd_variant (attention_fwd.hip) dispatches here in that
 // build.  Measured slower than the production variant 4 (docs/ARCHITECTURE.md,
 // profiles/r3_attn/, profiles/r3_pmc/): kept so the records can be re-run.
 #include "attention_common.h"
@@ -651,7 +651,7 @@ mxk_attn_fwd_w1_kernel(const uint16_t* __restrict__ q, const uint16_t* __restric
 }
 
 // ---------------------------------------------------------------------------
-// Launcher of the A/B records, called by mxk_attn_fwd_variant (attention.hip)
+// Launcher of the A/B records, called by mxk_attn_fwd_variant (attention_fwd.hip)
 // in the experiments build: the status, or -1 when the variant does not tile
 // the shape (the caller then runs variant 4).
 int mxk_attn_fwd_exp_launch(int variant, const uint16_t* qp, const uint16_t* kp, const uint16_t* vp,

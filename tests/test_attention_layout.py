@@ -1,4 +1,4 @@
-"""Host model of the LDS image used by native/kernels/attention.hip: 256-B
+"""Host model of the LDS image used by native/kernels/attention_fwd.hip: 256-B
 rows (128 bf16 of one key), 16-B chunk c of row r stored at
 c ^ ((r&3)<<2 | (r>>2)&3).  Checks that the K row reads (ds_read_b128, the
 A operand of the 32x32x16 S^T = K.Q^T MFMA) and the V transposed reads

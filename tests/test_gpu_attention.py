@@ -1,4 +1,4 @@
-"""GPU numerics of the hand-written flash attention (native/kernels/attention.hip)
+"""GPU numerics of the hand-written flash attention (native/kernels/attention_*.hip)
 against the fp32 PyTorch reference."""
 import math
 
@@ -327,3 +327,49 @@ def test_proj_rope_attention_fused(cuda_device, B, S, Hq, Hkv, causal):
         err = (got.float() - want).abs().max().item()
         tol = 5e-2 * max(1.0, want.abs().max().item())
         assert err < tol, (name, err, tol)
+
+
+def test_attn_bwd_rope_rejects_before_any_launch(cuda_device):
+    """mxk_attn_bwd_rope checks the whole layout - both kernels' - before its
+    first launch: with dv on a 2-byte but not 8-byte boundary, which only the
+    dK/dV kernel minds, it returns hipErrorInvalidValue and dq, dk, dv and
+    the workspace are untouched (the dQ kernel did not run).  With dv
+    aligned the same call is backward variant 9 plus the stand-alone RoPE
+    passes, bit for bit."""
+    from mxk8s.ops import _lib
+    from mxk8s.ops.fused import _rope_launch, rope_tables
+    B, S, Hq, Hkv, hd = 1, 256, 4, 1, 128
+    q, k, v = _qkv(B, S, Hq, Hkv, cuda_device, seed=47)
+    dout = torch.randn(B, S, Hq, hd, device=cuda_device,
+                       generator=torch.Generator(device=cuda_device).manual_seed(48)).bfloat16()
+    cos, sin = rope_tables(S, hd, device=cuda_device)
+    o, lse = A.attn_fwd(q, k, v, causal=True)
+    L = _lib.lib()
+    sentinel = 7.0
+    dq = torch.full((B, S, Hq, hd), sentinel, dtype=torch.bfloat16, device=cuda_device)
+    dk = torch.full((B, S, Hkv, hd), sentinel, dtype=torch.bfloat16, device=cuda_device)
+    dv = torch.full((B * S * Hkv * hd + 4,), sentinel, dtype=torch.bfloat16, device=cuda_device)
+    ws = torch.full((L.mxk_attn_bwd_workspace_variant(B, S, Hq, 9) // 4,), sentinel,
+                    dtype=torch.float32, device=cuda_device)
+
+    def call(dv_ptr):
+        st = L.mxk_attn_bwd_rope(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
+                                 dout.data_ptr(), lse.data_ptr(), dq.data_ptr(), dk.data_ptr(),
+                                 dv_ptr, ws.data_ptr(), B, S, Hq, Hkv, hd, q.stride(1),
+                                 k.stride(1), v.stride(1), dq.stride(1), dk.stride(1), Hkv * hd,
+                                 cos.data_ptr(), sin.data_ptr(), 1.0 / math.sqrt(hd), 1,
+                                 _lib.stream_ptr(cuda_device))
+        torch.cuda.synchronize()
+        return st
+
+    assert dv.data_ptr() % 8 == 0
+    assert call(dv.data_ptr() + 2) == 1     # hipErrorInvalidValue
+    for name, t in (("dq", dq), ("dk", dk), ("dv", dv), ("workspace", ws)):
+        assert bool((t == sentinel).all()), name
+
+    assert call(dv.data_ptr()) == 0
+    gq, gk, gv = A.attn_bwd(q, k, v, o, lse, dout, causal=True, variant=9)
+    assert torch.equal(dq, _rope_launch(gq, cos, sin, -1.0))
+    assert torch.equal(dk, _rope_launch(gk, cos, sin, -1.0))
+    assert torch.equal(dv[:B * S * Hkv * hd].view(B, S, Hkv, hd), gv)
+    assert bool((dv[B * S * Hkv * hd:] == sentinel).all())

@@ -179,8 +179,9 @@ def test_detector_flags_a_stale_descriptor_word():
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
-@pytest.mark.parametrize("src", ["attention.hip", "attention_bwd256.hip", "attention_fwd256.hip",
-                                 "attention_dq256.hip", "gemm_bf16.hip", "gemm_bf16_layouts.hip"])
+@pytest.mark.parametrize("src", ["attention_fwd.hip", "attention_bwd.hip", "attention_bwd256.hip",
+                                 "attention_fwd256.hip", "attention_dq256.hip", "gemm_bf16.hip",
+                                 "gemm_bf16_layouts.hip"])
 def test_asm_dma_reads_no_fresh_valu_sgpr(src, tmp_path):
     asm = _asm(src, str(tmp_path / (src + ".s")))
     assert "buffer_load" in asm
@@ -257,8 +258,8 @@ def trans_result_read_next(asm: str) -> list[str]:
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
-@pytest.mark.parametrize("src", ["attention.hip", "attention_bwd256.hip", "attention_fwd256.hip",
-                                 "attention_dq256.hip"])
+@pytest.mark.parametrize("src", ["attention_fwd.hip", "attention_bwd.hip", "attention_bwd256.hip",
+                                 "attention_fwd256.hip", "attention_dq256.hip"])
 def test_no_asm_read_of_a_fresh_transcendental(src, tmp_path):
     asm = _asm(src, str(tmp_path / "t.s"))
     assert trans_result_read_next(asm) == []
