@@ -29,7 +29,8 @@ LDLIBS_NODE := -ldl -lpthread
 
 KERNEL_SRCS := native/kernels/gemm_bf16.hip native/kernels/vector_add.hip \
                native/kernels/fused_ops.hip native/kernels/optim.hip native/kernels/attention_fwd.hip native/kernels/attention_bwd.hip native/kernels/attention_bwd256.hip native/kernels/attention_fwd256.hip native/kernels/attention_dq256.hip \
-               native/kernels/gemm_bf16_layouts.hip native/kernels/xent.hip native/kernels/contention.hip
+               native/kernels/gemm_bf16_layouts.hip native/kernels/xent.hip native/kernels/contention.hip \
+               native/kernels/gemm_mxfp8.hip
 KERNEL_OBJS := $(patsubst native/kernels/%.hip,$(BUILD)/kernels/%.o,$(KERNEL_SRCS))
 EXP_SRCS    := $(KERNEL_SRCS) $(wildcard native/kernels/experiments/*.hip)
 EXP_OBJS    := $(patsubst native/kernels/%.hip,$(BUILD)/exp/%.o,$(EXP_SRCS))
@@ -101,7 +102,8 @@ $(OUT_BIN)/mx-vector-add: $(BUILD)/tools/vector_add_main.o $(BUILD)/kernels/vect
 	@mkdir -p $(OUT_BIN)
 	$(HIPCC) --offload-arch=$(ARCH) -o $@ $^
 
-$(OUT_BIN)/mx-gemm-bench: $(BUILD)/tools/gemm_bench_main.o $(BUILD)/kernels/gemm_bf16.o $(BUILD)/kernels/gemm_bf16_layouts.o
+$(OUT_BIN)/mx-gemm-bench: $(BUILD)/tools/gemm_bench_main.o $(BUILD)/kernels/gemm_bf16.o $(BUILD)/kernels/gemm_bf16_layouts.o \
+                         $(BUILD)/kernels/gemm_mxfp8.o
 	@mkdir -p $(OUT_BIN)
 	$(HIPCC) --offload-arch=$(ARCH) -o $@ $^ -L$(ROCM)/lib -lrocblas -lrocprofiler-sdk-roctx -Wl,-rpath,$(ROCM)/lib
 

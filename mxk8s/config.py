@@ -56,6 +56,7 @@ TOLERATION = {"type": "object", "properties": {
     "effect": {"enum": ["NoSchedule", "PreferNoSchedule", "NoExecute", ""]}},
     "additionalProperties": False}
 VALIDATOR_TESTS = ["rocminfo", "vectoradd", "gemm", "rccl", "ddp"]
+GEMM_DTYPES = ["bf16", "mxfp8"]
 COLLECTIVES = ["allreduce", "reducescatter", "allgather", "alltoall"]
 
 VALUES: dict = {
@@ -142,7 +143,10 @@ VALUES: dict = {
                             maximum=8),
                   "tests": F("array", "", items={"enum": VALIDATOR_TESTS}),
                   "gemm": {"sizes": F("array", "", items={"type": "integer", "minimum": 256,
-                                                          "maximum": 65536})},
+                                                          "maximum": 65536}),
+                           "dtypes": F("array", "matrix paths of the GEMM test: bf16 MFMA, "
+                                                "mxfp8 block-scaled e4m3 MFMA",
+                                       items={"enum": GEMM_DTYPES})},
                   "rccl": {"minBytes": F("integer", "", minimum=1),
                            "maxBytes": F("integer", "", minimum=1, maximum=1 << 36),
                            "ops": F("array", "", items={"enum": COLLECTIVES})},

@@ -1,13 +1,18 @@
 """Hand-written CDNA4 (gfx950) HIP kernels exposed as torch ops.
 
 * :func:`gemm_bf16_tn`  — bf16 MFMA GEMM (validator config 3)
+* :func:`quantize_mxfp8`, :func:`gemm_mxfp8_tn` — MXFP8 (block-scaled e4m3) quantiser
+  and scaled-MFMA GEMM (validator config 3, ``--gemm-dtypes mxfp8``)
 * :func:`vector_add`    — smoke-test payload (config 2)
 * :func:`rmsnorm`, :func:`swiglu`, :func:`rope` — fused training ops (config 5)
 """
 from .gemm import gemm_bf16_tn, gemm_flops, is_fast_shape
+from .mxfp8 import (quantize_mxfp8, quantize_mxfp8_ref, dequantize_mxfp8, gemm_mxfp8_tn,
+                    is_fast_shape_mxfp8)
 from .vector_add import vector_add
 from .fused import rmsnorm, swiglu, rope, rope_tables
 from ._lib import kernels_available, KERNEL_LIB_PATH
 
-__all__ = ["gemm_bf16_tn", "gemm_flops", "is_fast_shape", "vector_add", "rmsnorm", "swiglu",
+__all__ = ["gemm_bf16_tn", "gemm_flops", "is_fast_shape", "quantize_mxfp8", "quantize_mxfp8_ref",
+           "dequantize_mxfp8", "gemm_mxfp8_tn", "is_fast_shape_mxfp8", "vector_add", "rmsnorm", "swiglu",
            "rope", "rope_tables", "kernels_available", "KERNEL_LIB_PATH"]

@@ -51,6 +51,9 @@ _SIGNATURES = {
     "mxk_stream_create_cu_masked_bits": (_i, [ctypes.POINTER(ctypes.c_int), _i, ctypes.POINTER(ctypes.c_void_p)]),
     "mxk_gemm_bf16_tn": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "mxk_gemm_bf16_tn_is_fast": (_i, [_i, _i, _i]),
+    "mxk_gemm_mxfp8_tn": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "mxk_gemm_mxfp8_tn_is_fast": (_i, [_i, _i, _i]),
+    "mxk_quantize_mxfp8": (_i, [_vp, _vp, _vp, _l, _i, _l, _l, _l, _vp]),
     "mxk_gemm_bf16_ex": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "mxk_gemm_bf16_ex_variant": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "mxk_gemm_bf16_ex_ws": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _l,

@@ -9,6 +9,9 @@ lines; the process exits non-zero if any test fails.
   rocminfo   the pod sees exactly the allocated gfx950 agents
   vectoradd  HIP vectoradd, bit-exact (bin/mx-vector-add)           config 2
   gemm       CDNA4 bf16 MFMA GEMM TFLOPS vs rocBLAS (bin/mx-gemm-bench) config 3
+             --gemm-dtypes bf16,mxfp8 adds the MXFP8 pass: block-scaled e4m3
+             operands quantised on the GPU, the scaled-MFMA GEMM checked against
+             the product of the dequantised operands (mx-gemm-bench --dtype mxfp8)
   rccl       RCCL all-reduce sweep over xGMI (bin/mx-allreduce-perf)  config 4
   ddp        Llama-3-8B DDP synthetic training step (bench.py --mode ddp) config 5
 
@@ -78,21 +81,48 @@ def test_vectoradd() -> bool:
     return rc == 0 and bool(rs) and all(r.get("pass") for r in rs)
 
 
-def test_gemm(sizes: str, gpus: int) -> bool:
-    rc, out = _run([os.path.join(BIN, "mx-gemm-bench"), "--sizes", sizes, "--devices", "all"],
-                   timeout=1800)
-    rs = results_from(out)
-    for r in rs:
-        emit(r)
-    if rs:
-        by = {}
+GEMM_DTYPES = ("bf16", "mxfp8")
+
+
+def parse_gemm_dtypes(arg: str) -> list[str]:
+    """``--gemm-dtypes``: a comma list of bf16 / mxfp8 without repeats."""
+    out = [d for d in arg.split(",") if d]
+    bad = [d for d in out if d not in GEMM_DTYPES]
+    if bad or not out or len(set(out)) != len(out):
+        raise ValueError(f"--gemm-dtypes must be a comma list of {'/'.join(GEMM_DTYPES)} "
+                         f"without repeats, got {arg!r}")
+    return out
+
+
+def test_gemm(sizes: str, gpus: int, dtypes=("bf16",)) -> bool:
+    """mx-gemm-bench once per dtype; every RESULT line is passed on and each
+    dtype gets a summary (the default bf16 one carries no "dtype" key, so a
+    default run prints what it always did).  Fails if any dtype fails."""
+    ok = True
+    for dtype in dtypes:
+        cmd = [os.path.join(BIN, "mx-gemm-bench"), "--sizes", sizes, "--devices", "all"]
+        if dtype != "bf16":
+            cmd += ["--dtype", dtype]
+        rc, out = _run(cmd, timeout=1800)
+        rs = results_from(out)
         for r in rs:
-            if "tflops" in r:
-                by.setdefault(r["M"], []).append(r["tflops"])
-        emit({"test": "gemm_summary", "gpus": gpus,
-              "aggregate_tflops": {str(k): round(sum(v), 1) for k, v in by.items()},
-              "pass": rc == 0})
-    return rc == 0 and bool(rs)
+            emit(r)
+        if rs:
+            by = {}
+            for r in rs:
+                if "tflops" in r:
+                    by.setdefault(r["M"], []).append(r["tflops"])
+            summary = {"test": "gemm_summary", "gpus": gpus,
+                       "aggregate_tflops": {str(k): round(sum(v), 1) for k, v in by.items()},
+                       "pass": rc == 0}
+            if dtype != "bf16":
+                summary = {"test": "gemm_summary", "dtype": dtype, **summary,
+                           "pass": rc == 0 and all(r.get("pass") for r in rs)}
+            emit(summary)
+        ok = ok and rc == 0 and bool(rs)
+        if dtype != "bf16":
+            ok = ok and all(r.get("pass") for r in rs)
+    return ok
 
 
 def test_gemm_profile(sizes: str, out_dir: str) -> bool:
@@ -162,6 +192,8 @@ def main(argv=None) -> int:
     p.add_argument("--tests", default="rocminfo,vectoradd,gemm,rccl")
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--gemm-sizes", default="4096,8192,16384")
+    p.add_argument("--gemm-dtypes", default="bf16",
+                   help="comma list of bf16,mxfp8: mx-gemm-bench runs once per dtype")
     p.add_argument("--rccl-min-bytes", type=int, default=8)
     p.add_argument("--rccl-max-bytes", type=int, default=1 << 33)
     p.add_argument("--rccl-scaling", default="")
@@ -175,6 +207,10 @@ def main(argv=None) -> int:
     p.add_argument("--debug", action="store_true",
                    help="serialise kernels (AMD_SERIALIZE_KERNEL=3, HIP_LAUNCH_BLOCKING=1)")
     a = p.parse_args(argv)
+    try:
+        gemm_dtypes = parse_gemm_dtypes(a.gemm_dtypes)
+    except ValueError as e:
+        p.error(str(e))
     if a.debug:
         _extra_env.update(DEBUG_ENV)
     tests = [t for t in a.tests.split(",") if t]
@@ -195,7 +231,7 @@ def main(argv=None) -> int:
         elif t == "vectoradd":
             status[t] = test_vectoradd()
         elif t == "gemm":
-            status[t] = test_gemm(a.gemm_sizes, a.gpus)
+            status[t] = test_gemm(a.gemm_sizes, a.gpus, gemm_dtypes)
             if a.profile:
                 status["gemm_profile"] = test_gemm_profile(a.gemm_sizes, a.profile_dir)
         elif t == "rccl":

@@ -1,0 +1,467 @@
+// MXFP8 (OCP MX, e4m3 elements, one E8M0 scale per 32 K elements) quantiser
+// and block-scaled MFMA GEMM for gfx950.
+//
+//   mxk_quantize_mxfp8   bf16 rows -> e4m3 bytes + E8M0 scale bytes
+//   mxk_gemm_mxfp8_tn    C[M][N] = dequant(A) . dequant(B)^T, fp32
+//                        accumulation, bf16 output; both operands K-contiguous
+//
+// ---- operand and scale lane map of v_mfma_scale_f32_32x32x64_f8f6f4 --------
+// (cbsz = blgp = 0: both operands e4m3; established with the one-hot test of
+// tests/test_gpu_mxfp8.py, which puts a distinct value and a distinct scale on
+// every (row, K-block))
+//   * lane l holds row (A operand) / column (B operand) l & 31; with h = l >> 5,
+//     the bytes of its first 4 operand VGPRs are k = 16 h + 0..15 and those of
+//     its last 4 VGPRs k = 32 + 16 h + 0..15, in memory order: each half of the
+//     8 VGPRs is laid out like the operand of a K = 32 instruction.  (Measured:
+//     with 32 consecutive k per lane every product at k % 64 in [16, 48) took
+//     the scale of the k-step's other block; unscaled, that permutation is
+//     invisible because both operands share it.)
+//   * so a lane holds 16 elements of each of the k-step's two MX blocks.  The
+//     scale of block b (k = 32 b .. 32 b + 31) of row r comes from the scale
+//     VGPR of lane r + 32 b; op_sel picks which of that register's 4 bytes.
+//   * C/D is the 32x32 map of every other dtype: column l & 31, row
+//     (reg & 3) + 8 (reg >> 2) + 4 (l >> 5).
+// The kernel hands the B fragment to the instruction's first operand, so the
+// lane index is the row of C and each lane owns runs of 4 consecutive columns.
+//
+// ---- structure --------------------------------------------------------------
+// 256x256 output tile, 4 waves (2 x 2, 128x128 each = 4 x 4 MFMA blocks), K-tile
+// of 128 elements = 128 B per row = two MFMA k-steps.  A K-tile costs the same
+// matrix-core time and stages the same bytes as a bf16 K-tile of 64
+// (gemm_tn_core.h); the LDS image (LDS-DMA, 16-B chunks XOR-swizzled by
+// (row >> 1) & 7) is the bf16 kernel's.  The 4 scale bytes of a row's K-tile
+// are one dword, staged by one 4-B LDS-DMA per wave and operand beside the
+// tile.  Two 66 KiB stages; one barrier per K-tile, in its middle:
+//   k-step 0 MFMAs  | k-step-1 fragments of stage t (buffer t & 1)
+//   lgkmcnt(0), vmcnt(0) (stage t+1 landed), barrier
+//   k-step 1 MFMAs  | DMA of stage t+2 into buffer t & 1, k-step-0 fragments
+//                     and scales of stage t+1
+// so a stage has one whole K-tile to land.  The MFMAs are the compiler
+// builtin: it places the hazard waits and the accumulators.
+#include "mx_common.h"
+
+namespace {
+
+constexpr int kBM = 256, kBN = 256, kBK = 128;
+constexpr int kThreads = 256;
+constexpr int kOpBytes = 256 * 128;              // 32 KiB per operand per stage
+constexpr int kScaleOff = 2 * kOpBytes;          // A scales, then B scales (1 KiB each)
+constexpr int kStageBytes = 2 * kOpBytes + 2048; // 66 KiB
+constexpr int kDmaPerStage = 18;                 // vector-memory ops per wave and stage
+
+typedef int i32x8_t __attribute__((ext_vector_type(8)));
+typedef int i32x4_t __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) void lds_void_t;
+
+// ---------------------------------------------------------------------------
+// Quantiser
+// ---------------------------------------------------------------------------
+// RNE of a finite fp32 with |v| <= 448 to an e4m3fn byte.
+__host__ __device__ inline uint32_t f32_to_e4m3(float v) {
+  uint32_t u;
+  __builtin_memcpy(&u, &v, 4);
+  const uint32_t sign = (u >> 24) & 0x80u;
+  u &= 0x7FFFFFFFu;
+  uint32_t r;
+  if (u >= 0x3C800000u) {                 // >= 2^-6: a normal e4m3
+    u += 0x7FFFFu + ((u >> 20) & 1u);     // round to 3 mantissa bits, ties to even
+    r = (u >> 20) - (120u << 3);          // rebias 127 -> 7
+  } else {                                // subnormal: units of 2^-9
+    float a;
+    __builtin_memcpy(&a, &u, 4);
+    a += 16384.0f;                        // 2^14: the sum's last bit is 2^-9
+    uint32_t b;
+    __builtin_memcpy(&b, &a, 4);
+    r = b - 0x46800000u;
+  }
+  return r | sign;
+}
+
+// floor(log2(amax)) - 8 clamped to [-127, 127]; 0 for amax == 0
+__host__ __device__ inline int mx_block_exp(float amax) {
+  uint32_t u;
+  __builtin_memcpy(&u, &amax, 4);
+  if (u == 0) return 0;
+  const int e = static_cast<int>(u >> 23) - 127 - 8;   // an fp32 subnormal lands below -127
+  return e < -127 ? -127 : e;                           // bf16 input: e <= 119
+}
+
+// One lane per 8 consecutive elements, 4 lanes (a DPP quad) per MX block.
+template <bool VEC>
+__global__ void __launch_bounds__(256)
+quantize_mxfp8_kernel(const uint16_t* __restrict__ x, uint8_t* __restrict__ q,
+                      uint8_t* __restrict__ s, long R, int K, long ldx, long ldq, long lds) {
+  const long per_row = K >> 3;
+  const long gid = static_cast<long>(blockIdx.x) * blockDim.x + threadIdx.x;
+  // K % 32 == 0, so a quad never straddles a row and leaves the grid whole
+  if (gid >= R * per_row) return;
+  const long row = gid / per_row;
+  const int c8 = static_cast<int>(gid - row * per_row);
+  const uint16_t* xp = x + row * ldx + c8 * 8;
+  uint32_t w[4];
+  if constexpr (VEC) {
+    const uint4 v = *reinterpret_cast<const uint4*>(xp);
+    w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) w[i] = xp[2 * i] | (static_cast<uint32_t>(xp[2 * i + 1]) << 16);
+  }
+  float f[8];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    f[2 * i] = __uint_as_float(w[i] << 16);
+    f[2 * i + 1] = __uint_as_float(w[i] & 0xFFFF0000u);
+  }
+  float amax = 0.f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) amax = fmaxf(amax, fabsf(f[i]));
+  // the block's other three lanes: quad_perm [1,0,3,2] then [2,3,0,1]
+  amax = fmaxf(amax, __uint_as_float(__builtin_amdgcn_mov_dpp(__float_as_uint(amax), 0xB1, 0xF, 0xF, true)));
+  amax = fmaxf(amax, __uint_as_float(__builtin_amdgcn_mov_dpp(__float_as_uint(amax), 0x4E, 0xF, 0xF, true)));
+  const int e = mx_block_exp(amax);
+  const float inv = __uint_as_float(static_cast<uint32_t>(127 - e) << 23);   // 2^-e
+  uint32_t out[2] = {0, 0};
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const float v = fminf(fmaxf(f[i] * inv, -448.f), 448.f);   // explicit saturation
+    out[i >> 2] |= f32_to_e4m3(v) << (8 * (i & 3));
+  }
+  uint8_t* qp = q + row * ldq + c8 * 8;
+  if constexpr (VEC) {
+    *reinterpret_cast<uint2*>(qp) = make_uint2(out[0], out[1]);
+  } else {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) qp[i] = static_cast<uint8_t>(out[i >> 2] >> (8 * (i & 3)));
+  }
+  if ((c8 & 3) == 0) s[row * lds + (c8 >> 2)] = static_cast<uint8_t>(e + 127);
+}
+
+// ---------------------------------------------------------------------------
+// GEMM
+// ---------------------------------------------------------------------------
+// LDS-DMA descriptor of one 256-row operand panel (bytes; gemm_tn_core.h DmaK
+// for 1-byte elements) and of its scale rows.
+struct Dma8 {
+  __amdgpu_buffer_rsrc_t rsrc;    // 256 rows of ld bytes
+  __amdgpu_buffer_rsrc_t srsrc;   // 256 rows of lds scale bytes
+  uint32_t voff;                  // row lane >> 3 of a piece, swizzled 16-B chunk
+  uint32_t svoff;                 // scale dword of row 64 wave + lane
+  int piece;                      // bytes between pieces (32 rows), scalar
+  int wave_off;                   // this wave's 8 rows inside a piece, scalar
+  // piece p: rows (4p + wave) 8 .. + 8; the row part rides in the scalar offset
+  __device__ __forceinline__ void issue(char* lds_op, char* lds_sc, int k_bytes, int wave) const {
+#pragma unroll
+    for (int p = 0; p < 8; ++p)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_t*)(lds_op + (p * 4 + wave) * 1024),
+                                               16, voff, k_bytes + wave_off + p * piece, 0, 0);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(srsrc, (lds_void_t*)(lds_sc + wave * 256), 4, svoff,
+                                             k_bytes >> 5, 0, 0);
+  }
+};
+
+__device__ __forceinline__ Dma8 make_dma8(const uint8_t* q, const uint8_t* sc, int ld, int lds,
+                                          int row0, int lane, int wave) {
+  Dma8 d;
+  d.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(q + static_cast<size_t>(row0) * ld),
+                                             0, 256 * ld, 0x00020000);
+  d.srsrc = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<uint8_t*>(sc + static_cast<size_t>(row0) * lds), 0, 256 * lds, 0x00020000);
+  const int r = lane >> 3;
+  const int c = (lane & 7) ^ ((4 * (wave & 1) + (r >> 1)) & 7);
+  d.voff = static_cast<uint32_t>(r * ld + c * 16);
+  d.piece = 32 * ld;
+  d.wave_off = wave * 8 * ld;
+  d.svoff = static_cast<uint32_t>((wave * 64 + lane) * lds);
+  return d;
+}
+
+__device__ __forceinline__ i32x8_t lds_frag(const char* p, int off_lo, int off_hi) {
+  const i32x4_t lo = *reinterpret_cast<const i32x4_t*>(p + off_lo);
+  const i32x4_t hi = *reinterpret_cast<const i32x4_t*>(p + off_hi);
+  return i32x8_t{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+}
+
+// Fragment byte offsets of this lane inside a 32-row block: k-step ks takes
+// the 16-B chunks 4 ks + (lane >> 5) (low 4 VGPRs) and 4 ks + 2 + (lane >> 5)
+// (high 4 VGPRs) of row lane & 31.
+struct FragOff {
+  int lo[2], hi[2];
+};
+
+struct Frags {
+  i32x8_t a[4], b[4];
+};
+
+// The 16 MFMAs of one k-step.  sa / sb: per row block the lane's scale dword,
+// already shifted so that byte 0 / 2 is block lane >> 5 of k-step 0 / 1.
+template <int KS>
+__device__ __forceinline__ void mfma_kstep(f32x16_t (&acc)[4][4], const Frags& f,
+                                           const int (&sa)[4], const int (&sb)[4]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(f.b[j], f.a[i], acc[i][j], 0, 0,
+                                                                  2 * KS, sb[j], 2 * KS, sa[i]);
+}
+
+__device__ __forceinline__ void read_frags(Frags& f, const char* stage, int a_base, int b_base,
+                                           const FragOff& fo, int ks) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    f.b[j] = lds_frag(stage + kOpBytes + b_base + j * 4096, fo.lo[ks], fo.hi[ks]);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) f.a[i] = lds_frag(stage + a_base + i * 4096, fo.lo[ks], fo.hi[ks]);
+}
+
+__device__ __forceinline__ void read_scales(int (&sa)[4], int (&sb)[4], const char* stage,
+                                            int a_row, int b_row, int shift) {
+  const int* pa = reinterpret_cast<const int*>(stage + kScaleOff) + a_row;
+  const int* pb = reinterpret_cast<const int*>(stage + kScaleOff + 1024) + b_row;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) sa[i] = static_cast<int>(static_cast<uint32_t>(pa[i * 32]) >> shift);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) sb[j] = static_cast<int>(static_cast<uint32_t>(pb[j * 32]) >> shift);
+}
+
+__device__ __forceinline__ void lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+__device__ __forceinline__ void block_barrier() {
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+}
+
+// K-tile t, read from stage buffer X (Y: the other one).  DMA: stage t+2
+// exists and goes out here, at k offset kb2 bytes (every K-tile but the last
+// two).  The reads of stage t+1 are unconditional: in the last K-tile they
+// fetch stale LDS that nothing uses, which keeps each loop to one body with
+// plain loop-carried registers.
+// The MFMAs are no memory operations, so the compiler would move them across
+// the waits; the sched barriers keep each k-step in its phase and interleave
+// it with that phase's LDS reads and DMA pieces (masks: 0x008 MFMA, 0x080 DS,
+// 0x010 vector memory).
+template <bool DMA>
+__device__ __forceinline__ void ktile(f32x16_t (&acc)[4][4], Frags& f0, int (&sa)[4], int (&sb)[4],
+                                      char* X, char* Y, const Dma8& dma_a, const Dma8& dma_b,
+                                      int a_base, int b_base, int a_row, int b_row, int shift,
+                                      const FragOff& fo, int kb2, int wave) {
+  Frags f1;
+  read_frags(f1, X, a_base, b_base, fo, 1);
+  mfma_kstep<0>(acc, f0, sa, sb);
+#pragma unroll
+  for (int k = 0; k < 16; ++k) {
+    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+    __builtin_amdgcn_sched_group_barrier(0x080, 1, 0);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  // every read of stage t retired; this wave's pieces of stage t+1 landed
+  lds_fence();
+  mxk::vm_wait_n<0>();
+  block_barrier();
+  __builtin_amdgcn_sched_barrier(0);
+  if constexpr (DMA) {
+    dma_a.issue(X, X + kScaleOff, kb2, wave);
+    dma_b.issue(X + kOpBytes, X + kScaleOff + 1024, kb2, wave);
+  }
+  int na[4], nb[4];
+  read_scales(na, nb, Y, a_row, b_row, shift);
+  read_frags(f0, Y, a_base, b_base, fo, 0);
+  mfma_kstep<1>(acc, f1, sa, sb);
+  // 24 LDS reads behind the first 8 MFMAs, the 18 DMA pieces spread over all 16
+  if constexpr (DMA) __builtin_amdgcn_sched_group_barrier(0x010, 2, 0);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+    __builtin_amdgcn_sched_group_barrier(0x080, 3, 0);
+    if constexpr (DMA) __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
+  }
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+    if constexpr (DMA) __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    sa[i] = na[i];
+    sb[i] = nb[i];
+  }
+}
+
+// bf16 store of a wave's 128x128 block through its LDS slice, two 64-row
+// passes with 272-B padded rows, read back row-major so every global store
+// covers 4 rows x 256 B (mx_common.h store_block_lds for the 32x32 C map:
+// lane = row, register group g = columns 8 g + 4 (lane >> 5) .. + 3).
+__device__ __forceinline__ void store_block32_lds(const f32x16_t (&acc)[4][4], uint16_t* C, int ldc,
+                                                  int row0, int col0, int lane, char* lds) {
+  const int r32 = lane & 31, h = lane >> 5;
+  const int rr = lane >> 4, cc = (lane & 15) * 8;
+#pragma unroll
+  for (int p = 0; p < 2; ++p) {
+#pragma unroll
+    for (int ii = 0; ii < 2; ++ii)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const f32x16_t& v = acc[2 * p + ii][j];
+          uint2 pk;
+          pk.x = mxk::pack2bf(v[4 * g], v[4 * g + 1]);
+          pk.y = mxk::pack2bf(v[4 * g + 2], v[4 * g + 3]);
+          *reinterpret_cast<uint2*>(lds + (ii * 32 + r32) * mxk::kStoreLdsRow +
+                                    (j * 32 + 8 * g + 4 * h) * 2) = pk;
+        }
+#pragma unroll
+    for (int it = 0; it < 16; ++it) {
+      const int r = it * 4 + rr;
+      const u32x4_t v = *reinterpret_cast<const u32x4_t*>(lds + r * mxk::kStoreLdsRow + cc * 2);
+      uint16_t* cp = C + static_cast<size_t>(row0 + p * 64 + r) * ldc + col0 + cc;
+      __builtin_nontemporal_store(v, reinterpret_cast<u32x4_t*>(cp));
+    }
+    __builtin_amdgcn_s_waitcnt(0xC07F);
+    __asm__ volatile("" ::: "memory");
+  }
+}
+
+__global__ void __launch_bounds__(kThreads, 1)
+mxk_gemm_mxfp8_tn_kernel(const uint8_t* __restrict__ Aq, const uint8_t* __restrict__ As,
+                         const uint8_t* __restrict__ Bq, const uint8_t* __restrict__ Bs,
+                         uint16_t* __restrict__ C, int M, int N, int K, int lda, int ldsa, int ldb,
+                         int ldsb, int ldc) {
+  static_assert(4 * mxk::kStoreLdsWave <= 2 * kStageBytes, "epilogue slices fit the stages");
+  __shared__ __attribute__((aligned(16))) char smem[2 * kStageBytes];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int wm = wave >> 1, wn = wave & 1;
+  int m0, n0;
+  mxk::w4b_tile<1>(blockIdx.x, gridDim.x, M / kBM, N / kBN, &m0, &n0);
+  const Dma8 dma_a = make_dma8(Aq, As, lda, ldsa, m0, lane, wave);
+  const Dma8 dma_b = make_dma8(Bq, Bs, ldb, ldsb, n0, lane, wave);
+  const int ns = K / kBK;
+
+  const int r32 = lane & 31, h = lane >> 5;
+  const int sw = (r32 >> 1) & 7;
+  FragOff fo;
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks) {
+    fo.lo[ks] = r32 * 128 + (((4 * ks + h) ^ sw) << 4);
+    fo.hi[ks] = r32 * 128 + (((4 * ks + 2 + h) ^ sw) << 4);
+  }
+  const int a_base = wm * 128 * 128, b_base = wn * 128 * 128;   // byte offset of the wave's rows
+  const int a_row = wm * 128 + r32, b_row = wn * 128 + r32;
+  const int shift = 8 * h;
+
+  f32x16_t acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  // An (empty) asm with an AGPR operand makes hipcc select the MFMAs' AGPR
+  // form, so the 256 accumulator registers live in the AGPR half of the file
+  // and the operands in the VGPR half; without it the builtin's VGPR form has
+  // to fit both into v0-v255 and spills.
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) asm volatile("" : "+a"(acc[i][j]));
+
+  // stages 0 and 1
+  dma_a.issue(smem, smem + kScaleOff, 0, wave);
+  dma_b.issue(smem + kOpBytes, smem + kScaleOff + 1024, 0, wave);
+  if (ns > 1) {
+    dma_a.issue(smem + kStageBytes, smem + kStageBytes + kScaleOff, kBK, wave);
+    dma_b.issue(smem + kStageBytes + kOpBytes, smem + kStageBytes + kScaleOff + 1024, kBK, wave);
+    mxk::vm_wait_n<kDmaPerStage>();
+  } else {
+    mxk::vm_wait_n<0>();
+  }
+  block_barrier();
+
+  Frags f0;
+  int sa[4], sb[4];
+  read_frags(f0, smem, a_base, b_base, fo, 0);
+  read_scales(sa, sb, smem, a_row, b_row, shift);
+
+  int kb2 = 2 * kBK;
+  int t = 0;
+#pragma clang loop unroll(disable)
+  for (; t + 2 < ns; ++t) {
+    char* X = smem + (t & 1) * kStageBytes;
+    char* Y = smem + ((t & 1) ^ 1) * kStageBytes;
+    ktile<true>(acc, f0, sa, sb, X, Y, dma_a, dma_b, a_base, b_base, a_row, b_row, shift, fo, kb2,
+                wave);
+    kb2 += kBK;
+  }
+  // the last two K-tiles (or the only one): no DMA
+#pragma clang loop unroll(disable)
+  for (; t < ns; ++t) {
+    char* X = smem + (t & 1) * kStageBytes;
+    char* Y = smem + ((t & 1) ^ 1) * kStageBytes;
+    ktile<false>(acc, f0, sa, sb, X, Y, dma_a, dma_b, a_base, b_base, a_row, b_row, shift, fo, 0,
+                 wave);
+  }
+
+  // every wave's last fragment reads retired before the slices overwrite the stages
+  lds_fence();
+  block_barrier();
+  store_block32_lds(acc, C, ldc, m0 + wm * 128, n0 + wn * 128, lane,
+                    smem + wave * mxk::kStoreLdsWave);
+}
+
+bool mxfp8_shape_ok(int M, int N, int K) {
+  return M > 0 && N > 0 && K > 0 && M % kBM == 0 && N % kBN == 0 && K % kBK == 0;
+}
+
+bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+}  // namespace
+
+MXK_API int mxk_gemm_mxfp8_tn_is_fast(int M, int N, int K) { return mxfp8_shape_ok(M, N, K) ? 1 : 0; }
+
+// Elements: 16-B aligned base, row stride a multiple of 16 B.  Scales: 4-B
+// aligned base, row stride a multiple of 4 B (one dword carries a K-tile's 4
+// block scales).  C: 16-B aligned, ldc % 8 == 0.  Row strides below 2^23.
+MXK_API int mxk_gemm_mxfp8_tn(const void* Aq, const void* As, const void* Bq, const void* Bs,
+                              void* C, int M, int N, int K, int lda, int ldsa, int ldb, int ldsb,
+                              int ldc, hipStream_t stream) {
+  if (!mxfp8_shape_ok(M, N, K) || !Aq || !As || !Bq || !Bs || !C)
+    return static_cast<int>(hipErrorInvalidValue);
+  constexpr int kMaxLd = 1 << 23;
+  if (lda < K || ldb < K || ldsa < K / 32 || ldsb < K / 32 || ldc < N || lda >= kMaxLd ||
+      ldb >= kMaxLd || ldsa >= kMaxLd || ldsb >= kMaxLd)
+    return static_cast<int>(hipErrorInvalidValue);
+  if (!aligned(Aq, 16) || !aligned(Bq, 16) || lda % 16 || ldb % 16 || !aligned(As, 4) ||
+      !aligned(Bs, 4) || ldsa % 4 || ldsb % 4 || !aligned(C, 16) || ldc % 8)
+    return static_cast<int>(hipErrorInvalidValue);
+  const int tiles = (M / kBM) * (N / kBN);
+  hipLaunchKernelGGL(mxk_gemm_mxfp8_tn_kernel, dim3(tiles), dim3(kThreads), 0, stream,
+                     static_cast<const uint8_t*>(Aq), static_cast<const uint8_t*>(As),
+                     static_cast<const uint8_t*>(Bq), static_cast<const uint8_t*>(Bs),
+                     static_cast<uint16_t*>(C), M, N, K, lda, ldsa, ldb, ldsb, ldc);
+  MXK_RETURN_LAUNCH_STATUS();
+}
+
+// x: bf16 [R][K] (row stride ldx elements), K % 32 == 0, finite values only.
+// q: e4m3 bytes [R][K] (row stride ldq), s: E8M0 bytes [R][K / 32] (row stride
+// lds).  Per block of 32: e = clamp(floor(log2(amax)) - 8, -127, 127), scale
+// byte e + 127 (127 for a zero block), element RNE(clamp(x 2^-e, +-448)).
+MXK_API int mxk_quantize_mxfp8(const void* x, void* q, void* s, long R, int K, long ldx, long ldq,
+                               long lds, hipStream_t stream) {
+  if (!x || !q || !s || R <= 0 || K <= 0 || K % 32 || ldx < K || ldq < K || lds < K / 32)
+    return static_cast<int>(hipErrorInvalidValue);
+  const long lanes = R * (K / 8);
+  const long blocks = (lanes + 255) / 256;
+  if (blocks > 0x7FFFFFFFL) return static_cast<int>(hipErrorInvalidValue);
+  const bool vec = aligned(x, 16) && ldx % 8 == 0 && aligned(q, 8) && ldq % 8 == 0;
+  if (vec)
+    hipLaunchKernelGGL(quantize_mxfp8_kernel<true>, dim3(static_cast<unsigned>(blocks)), dim3(256), 0,
+                       stream, static_cast<const uint16_t*>(x), static_cast<uint8_t*>(q),
+                       static_cast<uint8_t*>(s), R, K, ldx, ldq, lds);
+  else
+    hipLaunchKernelGGL(quantize_mxfp8_kernel<false>, dim3(static_cast<unsigned>(blocks)), dim3(256), 0,
+                       stream, static_cast<const uint16_t*>(x), static_cast<uint8_t*>(q),
+                       static_cast<uint8_t*>(s), R, K, ldx, ldq, lds);
+  MXK_RETURN_LAUNCH_STATUS();
+}

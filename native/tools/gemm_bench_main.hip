@@ -8,7 +8,14 @@
 // Protocol: >= warmup_ms of back-to-back launches, then the median of `iters`
 // hipEvent-timed launches (BASELINE.md "Measurement protocol").
 //   mx-gemm-bench [--sizes 4096,8192,16384] [--iters 50] [--warmup-ms 2000]
-//                 [--devices all|0,1] [--no-ref]
+//                 [--devices all|0,1] [--no-ref] [--dtype bf16|mxfp8]
+// --dtype mxfp8 runs the block-scaled e4m3 path instead
+// (native/kernels/gemm_mxfp8.hip): the same bf16 operands are quantised on the
+// GPU (32-element blocks, E8M0 scales), the scaled-MFMA kernel is checked on
+// the same 256x256 block against an fp32 fmaf chain over the DEQUANTISED
+// operands (fp8's own error against the bf16 product is ~7 %, so that product
+// is no reference), and timed by the same protocol.  rel_err_vs_rocblas is
+// null there: the binary has no library reference for the format.
 #include <hip/hip_runtime.h>
 #include <rocblas/rocblas.h>
 #include <rocprofiler-sdk-roctx/roctx.h>
@@ -28,6 +35,12 @@
 
 extern "C" int mxk_gemm_bf16_tn(const void* A, const void* Bt, void* C, int M, int N, int K, int lda,
                                 int ldb, int ldc, hipStream_t stream);
+
+extern "C" int mxk_gemm_mxfp8_tn(const void* Aq, const void* As, const void* Bq, const void* Bs,
+                                 void* C, int M, int N, int K, int lda, int ldsa, int ldb, int ldsb,
+                                 int ldc, hipStream_t stream);
+extern "C" int mxk_quantize_mxfp8(const void* x, void* q, void* s, long R, int K, long ldx, long ldq,
+                                  long lds, hipStream_t stream);
 
 namespace {
 
@@ -85,7 +98,37 @@ __global__ void spot_check(const uint16_t* A, const uint16_t* B, const uint16_t*
   atomicMax(max_ref, __float_as_uint(fabsf(acc)));
 }
 
+// e4m3fn byte -> fp32 (finite codes; 0x7f / 0xff, the NaNs, do not occur in a
+// quantiser's output) and E8M0 byte -> 2^(byte - 127), in plain C++
+__device__ float e4m3_to_f32(uint8_t b) {
+  const int e = (b >> 3) & 15, m = b & 7;
+  const float mag = e ? ldexpf(1.f + m * 0.125f, e - 7) : ldexpf(m * 0.125f, -6);
+  return b & 0x80 ? -mag : mag;
+}
+__device__ float e8m0_to_f32(uint8_t b) { return ldexpf(1.f, int(b) - 127); }
+
+// spot_check for the MXFP8 path: the reference is the fp32 fmaf chain over the
+// dequantised operands (element x block scale, both exact in fp32).
+__global__ void spot_check_mxfp8(const uint8_t* Aq, const uint8_t* As, const uint8_t* Bq,
+                                 const uint8_t* Bs, const uint16_t* C, int n, int r0, int c0,
+                                 unsigned* max_err, unsigned* max_ref) {
+  const int r = r0 + blockIdx.x, c = c0 + threadIdx.x;
+  const uint8_t* a = Aq + size_t(r) * n;
+  const uint8_t* b = Bq + size_t(c) * n;
+  const uint8_t* sa = As + size_t(r) * (n / 32);
+  const uint8_t* sb = Bs + size_t(c) * (n / 32);
+  float acc = 0.f;
+  for (int k = 0; k < n; ++k)
+    acc = fmaf(e4m3_to_f32(a[k]) * e8m0_to_f32(sa[k >> 5]), e4m3_to_f32(b[k]) * e8m0_to_f32(sb[k >> 5]),
+               acc);
+  const float got = __uint_as_float(uint32_t(C[size_t(r) * n + c]) << 16);
+  const float err = fabsf(got - acc);
+  atomicMax(max_err, __float_as_uint(err == err ? err : INFINITY));   // NaN -> inf
+  atomicMax(max_ref, __float_as_uint(fabsf(acc)));
+}
+
 struct Opts {
+  bool mxfp8 = false;
   std::vector<int> sizes{4096, 8192, 16384};
   int iters = 50;
   int warmup_ms = 2000;
@@ -229,6 +272,126 @@ bool run_device(int dev, const Opts& o) {
   return all_ok;
 }
 
+// --dtype mxfp8: quantise, poison, launch, spot-check against the dequantised
+// operands, then the bf16 path's warm-up floor and median-of-iters timing.
+bool run_device_mxfp8(int dev, const Opts& o) {
+  bool all_ok = true;
+  if (hipSetDevice(dev) != hipSuccess) return false;
+  hipStream_t st;
+  CK(hipStreamCreate(&st));
+  for (int n : o.sizes) {
+    const size_t elems = size_t(n) * n;
+    const int nb = n / 32;
+    uint16_t *A = nullptr, *B = nullptr, *C = nullptr;
+    uint8_t *Aq = nullptr, *Bq = nullptr, *As = nullptr, *Bs = nullptr;
+    if (hipMalloc(&A, elems * 2) || hipMalloc(&B, elems * 2) || hipMalloc(&C, elems * 2) ||
+        hipMalloc(&Aq, elems) || hipMalloc(&Bq, elems) || hipMalloc(&As, size_t(n) * nb) ||
+        hipMalloc(&Bs, size_t(n) * nb)) {
+      std::lock_guard<std::mutex> lk(g_print);
+      std::printf("RESULT {\"test\":\"gemm\",\"gpu\":%d,\"M\":%d,\"dtype\":\"mxfp8\",\"pass\":false,"
+                  "\"error\":\"alloc\"}\n", dev, n);
+      all_ok = false;
+      for (void* p : {(void*)A, (void*)B, (void*)C, (void*)Aq, (void*)Bq, (void*)As, (void*)Bs})
+        if (p) CK(hipFree(p));
+      continue;
+    }
+    hipLaunchKernelGGL(fill_uniform_bf16, dim3(2048), dim3(256), 0, st, A, elems, 0x1234u + dev);
+    hipLaunchKernelGGL(fill_uniform_bf16, dim3(2048), dim3(256), 0, st, B, elems, 0x9876u + dev);
+    std::string err_msg;
+    hipEvent_t e0, e1;
+    CK(hipEventCreate(&e0));
+    CK(hipEventCreate(&e1));
+    // quantise both operands on the GPU (run once untimed, then timed)
+    int qst = mxk_quantize_mxfp8(A, Aq, As, n, n, n, n, nb, st);
+    if (!qst) qst = mxk_quantize_mxfp8(B, Bq, Bs, n, n, n, n, nb, st);
+    CK(hipEventRecord(e0, st));
+    if (!qst) qst = mxk_quantize_mxfp8(A, Aq, As, n, n, n, n, nb, st);
+    if (!qst) qst = mxk_quantize_mxfp8(B, Bq, Bs, n, n, n, n, nb, st);
+    CK(hipEventRecord(e1, st));
+    CK(hipEventSynchronize(e1));
+    float quantize_ms = 0;
+    CK(hipEventElapsedTime(&quantize_ms, e0, e1));
+    if (qst != 0)
+      err_msg = std::string("quantiser launch failed: ") + hipGetErrorString(static_cast<hipError_t>(qst));
+    // poison C first: a launch that silently did nothing cannot pass
+    CK(hipMemsetAsync(C, 0xff, elems * 2, st));
+    const char* skip = std::getenv("MXK_GEMM_BENCH_SKIP_KERNEL");   // fault-injection hook
+    int launch_st = 0;
+    if (!(skip && *skip == '1'))
+      launch_st = mxk_gemm_mxfp8_tn(Aq, As, Bq, Bs, C, n, n, n, n, nb, n, nb, n, st);
+    const hipError_t le = hipGetLastError();
+    if (err_msg.empty() && (launch_st != 0 || le != hipSuccess))
+      err_msg = std::string("kernel launch failed: ") +
+                hipGetErrorString(launch_st ? static_cast<hipError_t>(launch_st) : le);
+    // fp32 spot check of the bf16 path's pseudo-random 256x256 block
+    unsigned* dmax = nullptr;
+    unsigned hmax[2] = {0, 0};
+    CK(hipMalloc(&dmax, 8));
+    CK(hipMemsetAsync(dmax, 0, 8, st));
+    const uint32_t h32 = (0x9E3779B1u * uint32_t(n)) ^ (0x85EBCA6Bu * uint32_t(dev + 1));
+    const int blocks = n / 256;
+    const int r0 = int(h32 % uint32_t(blocks)) * 256, c0 = int((h32 >> 16) % uint32_t(blocks)) * 256;
+    hipLaunchKernelGGL(spot_check_mxfp8, dim3(256), dim3(256), 0, st, Aq, As, Bq, Bs, C, n, r0, c0,
+                       dmax, dmax + 1);
+    CK(hipGetLastError());
+    CK(hipMemcpyAsync(hmax, dmax, 8, hipMemcpyDeviceToHost, st));
+    CK(hipStreamSynchronize(st));
+    CK(hipFree(dmax));
+    float max_abs_err, max_ref;
+    std::memcpy(&max_abs_err, &hmax[0], 4);
+    std::memcpy(&max_ref, &hmax[1], 4);
+    const float spot_tol = 0.0078125f * max_ref;   // 2^-7 max|ref|: bf16 output rounding is 2^-8
+    const bool spot_ok = max_ref > 0.f && max_abs_err <= spot_tol;
+    if (err_msg.empty() && !spot_ok)
+      err_msg = max_ref > 0.f ? "fp32 spot check failed" : "fp32 spot check: reference block is zero";
+    float spent = 0;
+    roctxRangePushA("gemm_mxfp8.warmup");
+    while (spent < o.warmup_ms) {
+      CK(hipEventRecord(e0, st));
+      for (int i = 0; i < 10; ++i) mxk_gemm_mxfp8_tn(Aq, As, Bq, Bs, C, n, n, n, n, nb, n, nb, n, st);
+      CK(hipEventRecord(e1, st));
+      CK(hipEventSynchronize(e1));
+      float ms;
+      CK(hipEventElapsedTime(&ms, e0, e1));
+      spent += ms;
+    }
+    roctxRangePop();
+    std::vector<float> t(o.iters);
+    roctxRangePushA("gemm_mxfp8.timed");
+    for (int i = 0; i < o.iters; ++i) {
+      CK(hipEventRecord(e0, st));
+      mxk_gemm_mxfp8_tn(Aq, As, Bq, Bs, C, n, n, n, n, nb, n, nb, n, st);
+      CK(hipEventRecord(e1, st));
+      CK(hipEventSynchronize(e1));
+      CK(hipEventElapsedTime(&t[i], e0, e1));
+    }
+    roctxRangePop();
+    std::sort(t.begin(), t.end());
+    const double med = t[t.size() / 2] * 1e-3;
+    const double tflops = 2.0 * n * double(n) * n / med / 1e12;
+    const bool pass = err_msg.empty();
+    all_ok &= pass;
+    {
+      std::lock_guard<std::mutex> lk(g_print);
+      std::printf("RESULT {\"test\":\"gemm\",\"gpu\":%d,\"M\":%d,\"N\":%d,\"K\":%d,\"dtype\":\"mxfp8\","
+                  "\"median_ms\":%.4f,\"min_ms\":%.4f,\"tflops\":%.1f,\"rel_err_vs_rocblas\":null,"
+                  "\"spot_block\":[%d,%d],\"max_abs_err\":%s,\"spot_tolerance\":%.4g,"
+                  "\"quantize_ms\":%.4f,\"pass\":%s%s%s%s}\n",
+                  dev, n, n, n, med * 1e3, t[0], tflops, r0, c0, json_num(max_abs_err).c_str(),
+                  spot_tol, quantize_ms,
+                  pass ? "true" : "false", err_msg.empty() ? "" : ",\"error\":\"",
+                  err_msg.c_str(), err_msg.empty() ? "" : "\"");
+      std::fflush(stdout);
+    }
+    CK(hipEventDestroy(e0));
+    CK(hipEventDestroy(e1));
+    for (void* p : {(void*)A, (void*)B, (void*)C, (void*)Aq, (void*)Bq, (void*)As, (void*)Bs})
+      CK(hipFree(p));
+  }
+  CK(hipStreamDestroy(st));
+  return all_ok;
+}
+
 std::vector<int> parse_list(const char* s) {
   std::vector<int> v;
   std::stringstream ss(s);
@@ -247,7 +410,11 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[i], "--iters") && i + 1 < argc) o.iters = std::max(1, std::atoi(argv[++i]));
     else if (!std::strcmp(argv[i], "--warmup-ms") && i + 1 < argc) o.warmup_ms = std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--no-ref")) o.ref = false;
-    else if (!std::strcmp(argv[i], "--devices") && i + 1 < argc) {
+    else if (!std::strcmp(argv[i], "--dtype") && i + 1 < argc) {
+      const char* v = argv[++i];
+      if (!std::strcmp(v, "mxfp8")) o.mxfp8 = true;
+      else if (std::strcmp(v, "bf16")) { std::fprintf(stderr, "--dtype must be bf16 or mxfp8\n"); return 2; }
+    } else if (!std::strcmp(argv[i], "--devices") && i + 1 < argc) {
       const char* v = argv[++i];
       if (std::strcmp(v, "all")) { o.devices = parse_list(v); all = false; }
     } else { std::fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
@@ -262,7 +429,8 @@ int main(int argc, char** argv) {
   if (all) for (int d = 0; d < count; ++d) o.devices.push_back(d);
   std::atomic<bool> ok{true};
   std::vector<std::thread> th;
-  for (int d : o.devices) th.emplace_back([&, d] { if (!run_device(d, o)) ok = false; });
+  for (int d : o.devices)
+    th.emplace_back([&, d] { if (!(o.mxfp8 ? run_device_mxfp8(d, o) : run_device(d, o))) ok = false; });
   for (auto& t : th) t.join();
   return ok ? 0 : 1;
 }
