@@ -46,6 +46,16 @@ class LlamaConfig:
     norm_eps: float = 1e-5
     rope_theta: float = 500000.0
     max_seq_len: int = 8192
+    # "mxfp8" (opt-in): wqkv, wo, w13 and w2 run their three products on the
+    # MXFP8 GEMM (mxk8s.ops.linear.linear_mxfp8) without the fused RoPE / SwiGLU
+    # epilogues, which are bf16 kernels; lm_head and everything that is not a
+    # linear layer stay bf16
+    linear_dtype: str = "bf16"
+
+    def __post_init__(self):
+        if self.linear_dtype not in Linear.COMPUTE:
+            raise ValueError(f"linear_dtype must be one of {Linear.COMPUTE}, "
+                             f"got {self.linear_dtype!r}")
 
     @classmethod
     def llama3_8b(cls) -> "LlamaConfig":
@@ -92,8 +102,8 @@ class Attention(nn.Module):
         super().__init__()
         self.cfg = cfg
         hd = cfg.head_dim
-        self.wqkv = Linear(cfg.dim, (cfg.n_heads + 2 * cfg.n_kv_heads) * hd)
-        self.wo = Linear(cfg.n_heads * hd, cfg.dim)
+        self.wqkv = Linear(cfg.dim, (cfg.n_heads + 2 * cfg.n_kv_heads) * hd, compute=cfg.linear_dtype)
+        self.wo = Linear(cfg.n_heads * hd, cfg.dim, compute=cfg.linear_dtype)
 
     def forward(self, x, cos, sin):
         B, S, _ = x.shape
@@ -101,8 +111,10 @@ class Attention(nn.Module):
         hd = c.head_dim
         # projection + RoPE (in the GEMM's epilogue) + flash attention as one
         # node; its backward takes d(qkv) from the attention kernels with the
-        # RoPE backward fused into their stores
-        o = proj_rope_attention(x, self.wqkv.weight, cos, sin, c.n_heads, c.n_kv_heads, hd)
+        # RoPE backward fused into their stores (a bf16 GEMM: not with mxfp8 linears)
+        o = None
+        if c.linear_dtype == "bf16":
+            o = proj_rope_attention(x, self.wqkv.weight, cos, sin, c.n_heads, c.n_kv_heads, hd)
         if o is not None:
             return self.wo(o.reshape(B, S, c.n_heads * hd))
         qkv = self.wqkv(x)
@@ -126,13 +138,14 @@ class Attention(nn.Module):
 class MLP(nn.Module):
     def __init__(self, cfg: LlamaConfig):
         super().__init__()
-        self.w13 = Linear(cfg.dim, 2 * cfg.ffn_dim)   # [gate | up]
+        self.mxfp8 = cfg.linear_dtype == "mxfp8"
+        self.w13 = Linear(cfg.dim, 2 * cfg.ffn_dim, compute=cfg.linear_dtype)   # [gate | up]
         # w2(swiglu(.)) as one node: the SwiGLU backward runs in the epilogue
         # of w2's input-gradient GEMM
-        self.w2 = SwiGLULinear(cfg.ffn_dim, cfg.dim)
+        self.w2 = SwiGLULinear(cfg.ffn_dim, cfg.dim, compute=cfg.linear_dtype)
 
     def forward(self, x):
-        if x.is_cuda and x.dtype == torch.bfloat16:
+        if x.is_cuda and x.dtype == torch.bfloat16 and not self.mxfp8:
             # one node: up-projection with SwiGLU in its epilogue, down
             # projection, fused dgrad-SwiGLU backward (mxk8s.ops.linear)
             return swiglu_mlp(x, self.w13.weight, self.w2.weight)

@@ -108,6 +108,102 @@ class _LinearFn(torch.autograd.Function):
         return dx, dw
 
 
+# ---- MXFP8 (opt-in) ---------------------------------------------------------
+# gemm_mxfp8_tn contracts over the contiguous axis of both operands, and an MX
+# block lies along the contracted axis:
+#   y  = x W^T      x [T, in] and W [out, in] quantised along their rows
+#   dx = dy W       dy [T, out] along its rows, W along its columns: the
+#                   transposed image quantize_mxfp8_t(W) [in, out]
+#   dW = dy^T x     both along the token axis: quantize_mxfp8_t(dy) [out, T]
+#                   and quantize_mxfp8_t(x) [in, T]
+# dy is read once for both of its images (quantize_mxfp8_dual).
+_MX_TILE = 256
+
+
+def is_mxfp8_linear_shape(T: int, in_features: int, out_features: int) -> bool:
+    """True when ``linear_mxfp8`` takes the shape: tokens, in and out features
+    all positive multiples of 256, which gives M, N % 256 and K % 128 in each
+    of the three products and scale rows that are whole dwords."""
+    return all(n > 0 and n % _MX_TILE == 0 for n in (T, in_features, out_features))
+
+
+def _bf16_rows(t: torch.Tensor) -> torch.Tensor:
+    """bf16 and unit inner stride (a row stride larger than the width stays)."""
+    if t.dtype != torch.bfloat16:
+        t = t.to(torch.bfloat16)
+    return t if t.stride(1) == 1 else t.contiguous()
+
+
+def _mx_weight_grad(weight: torch.Tensor, dyt, xt):
+    """_weight_grad on the MXFP8 GEMM: dW = dequant(dy^T) dequant(x^T)^T."""
+    from .mxfp8 import gemm_mxfp8_tn
+    sink = getattr(weight, "main_grad", None)
+    if sink is None:
+        return gemm_mxfp8_tn(*dyt, *xt).to(weight.dtype)
+    if weight._mxk_grad_fresh:
+        if sink.dtype == torch.bfloat16:
+            gemm_mxfp8_tn(*dyt, *xt, out=sink)
+        else:                                   # an fp32 flat buffer: the GEMM's output is bf16
+            sink.copy_(gemm_mxfp8_tn(*dyt, *xt))
+        weight._mxk_grad_fresh = False
+    else:
+        sink.add_(gemm_mxfp8_tn(*dyt, *xt))
+    ready = getattr(weight, "_mxk_grad_ready", None)
+    if ready is not None:
+        ready()
+    return None
+
+
+class _LinearMxfp8Fn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight):
+        from .mxfp8 import gemm_mxfp8_tn, quantize_mxfp8
+        ctx.save_for_backward(x, weight)      # bf16, as _LinearFn: no quantised copy is held
+        x2 = _bf16_rows(x.reshape(-1, x.shape[-1]))
+        y = gemm_mxfp8_tn(*quantize_mxfp8(x2), *quantize_mxfp8(_bf16_rows(weight)))
+        return y.to(x.dtype).view(*x.shape[:-1], weight.shape[0])
+
+    @staticmethod
+    def backward(ctx, dy):
+        from .mxfp8 import gemm_mxfp8_tn, quantize_mxfp8, quantize_mxfp8_dual, quantize_mxfp8_t
+        x, weight = ctx.saved_tensors
+        need_x, need_w = ctx.needs_input_grad
+        dy2 = _bf16_rows(dy.reshape(-1, dy.shape[-1]))
+        if need_x and need_w:
+            dq, ds, dqt, dst = quantize_mxfp8_dual(dy2)
+        elif need_x:
+            dq, ds = quantize_mxfp8(dy2)
+        elif need_w:
+            dqt, dst = quantize_mxfp8_t(dy2)
+        dx = dw = None
+        if need_x:
+            dx = gemm_mxfp8_tn(dq, ds, *quantize_mxfp8_t(_bf16_rows(weight)))
+            dx = dx.to(x.dtype).view(x.shape)
+        if need_w:
+            x2 = _bf16_rows(x.reshape(-1, x.shape[-1]))
+            dw = _mx_weight_grad(weight, (dqt, dst), quantize_mxfp8_t(x2))
+        return dx, dw
+
+
+def linear_mxfp8(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
+    """``x @ weight.T`` whose forward product, input gradient and weight gradient
+    all run on the MXFP8 GEMM (``gemm_mxfp8_tn``), each operand quantised in
+    blocks of 32 along the axis its product contracts.  ``x`` is ``[..., in]``,
+    ``weight`` ``[out, in]``; tensors that are not bf16 are cast to bf16 for
+    quantising and the results returned in their own dtype.  The weight
+    gradient keeps the ``main_grad`` contract of :class:`Linear`.  Raises
+    ``ValueError`` unless :func:`is_mxfp8_linear_shape` holds."""
+    if weight.dim() != 2 or x.dim() < 1 or x.shape[-1] != weight.shape[1]:
+        raise ValueError(f"linear_mxfp8: x {tuple(x.shape)} does not match weight "
+                         f"{tuple(weight.shape)}")
+    T = x.numel() // x.shape[-1] if x.shape[-1] else 0
+    if not is_mxfp8_linear_shape(T, weight.shape[1], weight.shape[0]):
+        raise ValueError("linear_mxfp8 needs tokens, in_features and out_features to be positive "
+                         f"multiples of {_MX_TILE}, got T={T} in={weight.shape[1]} "
+                         f"out={weight.shape[0]}")
+    return _LinearMxfp8Fn.apply(x, weight)
+
+
 # y = swiglu(gu) W^T with the SwiGLU backward fused into the input-gradient
 # GEMM's epilogue (mxk_gemm_bf16_dgrad_swiglu): d(act) = dy W never goes to
 # HBM (0.94 GB less traffic per Llama-3-8B layer, no separate element-wise
@@ -219,13 +315,26 @@ def swiglu_mlp(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor) -> torch.Te
 
 
 class Linear(nn.Linear):
-    """``nn.Linear(bias=False)`` with the direct-to-flat-buffer weight gradient."""
+    """``nn.Linear(bias=False)`` with the direct-to-flat-buffer weight gradient.
 
-    def __init__(self, in_features: int, out_features: int, **kw):
+    ``compute="mxfp8"`` (opt-in) runs the three products of a call on the
+    MXFP8 GEMM (:func:`linear_mxfp8`) when :func:`is_mxfp8_linear_shape` holds
+    for it, i.e. tokens, in and out features are multiples of 256.  Any other
+    call (toy shapes, a ragged batch) silently takes the bf16 path."""
+
+    COMPUTE = ("bf16", "mxfp8")
+
+    def __init__(self, in_features: int, out_features: int, compute: str = "bf16", **kw):
+        if compute not in self.COMPUTE:
+            raise ValueError(f"compute must be one of {self.COMPUTE}, got {compute!r}")
         super().__init__(in_features, out_features, bias=False, **kw)
+        self.compute = compute
         self.weight._mxk_direct_grad = True
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if self.compute == "mxfp8" and is_mxfp8_linear_shape(
+                x.numel() // self.in_features, self.in_features, self.out_features):
+            return _LinearMxfp8Fn.apply(x, self.weight)
         return _LinearFn.apply(x, self.weight)
 
 
@@ -233,10 +342,11 @@ class SwiGLULinear(Linear):
     """Down projection applied to swiglu(gu), gu = [gate | up] of width
     2 * in_features: ``w2(swiglu(gu))`` as one node whose backward fuses the
     SwiGLU gradient into the input-gradient GEMM.  CPU / non-bf16 inputs take
-    the plain composition."""
+    the plain composition, and so does ``compute="mxfp8"``: the fused
+    dgrad-SwiGLU kernel is a bf16 kernel."""
 
     def forward(self, gu: torch.Tensor) -> torch.Tensor:
-        if gu.device.type == "cpu" or gu.dtype != torch.bfloat16:
+        if gu.device.type == "cpu" or gu.dtype != torch.bfloat16 or self.compute == "mxfp8":
             from .fused import swiglu
             return super().forward(swiglu(gu))
         return _SwiGLULinearFn.apply(gu, self.weight)

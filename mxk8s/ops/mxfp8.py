@@ -21,6 +21,11 @@ fp32 accumulation and bf16 output on ``v_mfma_scale_f32_32x32x64_f8f6f4``.
 The product of the *dequantised* operands is the reference of every check:
 against the unquantised bf16 product the format's own error is about 7 %.
 
+``quantize_mxfp8_t(x)`` and ``quantize_mxfp8_dual(x)`` give the images of the
+transposed tensor, whose blocks are 32 consecutive *rows* of ``x``, without a
+transposed copy: what the backward products of a linear layer contract over
+(``mxk8s.ops.linear.linear_mxfp8``).
+
 GPU tensors always run the hand-written kernels (no fallback); CPU tensors
 take the pure-torch reference path.
 """
@@ -80,6 +85,61 @@ def quantize_mxfp8(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
                                        q.stride(0), s.stride(0), _lib.stream_ptr(x.device))
     _lib.check(st, "mxk_quantize_mxfp8")
     return q, s
+
+
+def _check_xt(x: torch.Tensor, dual: bool) -> None:
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("x must be a tensor")
+    if x.dtype != torch.bfloat16:
+        raise TypeError(f"x must be bfloat16, got {x.dtype}")
+    if x.dim() != 2:
+        raise ValueError(f"x must be 2-D, got shape {tuple(x.shape)}")
+    R, C = x.shape
+    if R == 0 or C == 0 or R % BLOCK or (dual and C % BLOCK):
+        raise ValueError(f"x must be [R, C] with R a positive multiple of {BLOCK} and C "
+                         + (f"a positive multiple of {BLOCK}" if dual else "> 0")
+                         + f", got {tuple(x.shape)}")
+    if x.stride(1) != 1:
+        raise ValueError("x must be row-major (stride(1) == 1)")
+
+
+def quantize_mxfp8_t(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """bf16 ``[R, C]`` -> (e4m3 ``[C, R]``, uint8 E8M0 scales ``[C, R/32]``): the
+    images of ``quantize_mxfp8(x.t().contiguous())``, bit for bit, from one pass
+    over ``x``.  The MX blocks are 32 consecutive *rows* of ``x`` (``R % 32 ==
+    0``; any ``C``), which is what a product contracting over the row axis of
+    ``x`` needs.  Finite inputs only.  A row stride larger than C is fine."""
+    _check_xt(x, dual=False)
+    if x.device.type == "cpu":
+        return quantize_mxfp8_ref(x.t().contiguous())
+    R, C = x.shape
+    qt = torch.empty((C, R), dtype=torch.float8_e4m3fn, device=x.device)
+    st = torch.empty((C, R // BLOCK), dtype=torch.uint8, device=x.device)
+    rc = _lib.lib().mxk_quantize_mxfp8_t(x.data_ptr(), qt.data_ptr(), st.data_ptr(), R, C,
+                                         x.stride(0), qt.stride(0), st.stride(0),
+                                         _lib.stream_ptr(x.device))
+    _lib.check(rc, "mxk_quantize_mxfp8_t")
+    return qt, st
+
+
+def quantize_mxfp8_dual(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor,
+                                                  torch.Tensor]:
+    """``(q, s, qt, st)``: ``quantize_mxfp8(x)`` and ``quantize_mxfp8_t(x)`` from
+    one read of ``x`` (bf16 ``[R, C]``, both multiples of 32)."""
+    _check_xt(x, dual=True)
+    if x.device.type == "cpu":
+        return quantize_mxfp8_ref(x) + quantize_mxfp8_ref(x.t().contiguous())
+    R, C = x.shape
+    q = torch.empty((R, C), dtype=torch.float8_e4m3fn, device=x.device)
+    s = torch.empty((R, C // BLOCK), dtype=torch.uint8, device=x.device)
+    qt = torch.empty((C, R), dtype=torch.float8_e4m3fn, device=x.device)
+    st = torch.empty((C, R // BLOCK), dtype=torch.uint8, device=x.device)
+    rc = _lib.lib().mxk_quantize_mxfp8_dual(x.data_ptr(), q.data_ptr(), s.data_ptr(), qt.data_ptr(),
+                                            st.data_ptr(), R, C, x.stride(0), q.stride(0),
+                                            s.stride(0), qt.stride(0), st.stride(0),
+                                            _lib.stream_ptr(x.device))
+    _lib.check(rc, "mxk_quantize_mxfp8_dual")
+    return q, s, qt, st
 
 
 def _check_pair(q: torch.Tensor, s: torch.Tensor, qn: str, sn: str) -> None:

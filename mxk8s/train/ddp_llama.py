@@ -59,6 +59,16 @@ def use_tuned_gemms(path: str = TUNED_GEMMS) -> bool:
     return bool(tunable.read_file(path))
 
 
+def resolve_linear_dtype(args) -> str:
+    """``--linear-dtype``, else the environment variable ``MXK_LINEAR_DTYPE``
+    (so ``bench.py --mode ddp`` can be A/B'd unchanged), else bf16.  An unknown
+    value is an error."""
+    v = getattr(args, "linear_dtype", None) or os.environ.get("MXK_LINEAR_DTYPE") or "bf16"
+    if v not in ("bf16", "mxfp8"):
+        raise ValueError(f"linear dtype must be bf16 or mxfp8, got {v!r}")
+    return v
+
+
 def build(cfg: LlamaConfig, device: torch.device, bucket_mb: float, lr: float = 3e-4,
           zero: bool = True, overlap: bool | None = None, reduce_dtype: str = "bf16",
           gather_overlap: bool = True):
@@ -132,6 +142,7 @@ def run_ddp_bench(args) -> dict:
         dev = torch.device("cpu")
         backend = "gloo"
     mxdist.init_distributed(backend=backend, device=dev if backend == "nccl" else None)
+    linear_dtype = resolve_linear_dtype(args)
     cfg = LlamaConfig.llama3_8b()
     model_name = "Llama-3-8B"
     if getattr(args, "layers", None):
@@ -140,6 +151,7 @@ def run_ddp_bench(args) -> dict:
     if getattr(args, "tiny", False):
         cfg = LlamaConfig.tiny()
         model_name = "tiny-llama (test)"
+    cfg.linear_dtype = linear_dtype
     seq, mb = args.seq_len, args.micro_batch
     bucket_mb = getattr(args, "bucket_mb", 512.0)
     # the TunableOp table only matters when a library GEMM runs in the step
@@ -206,6 +218,7 @@ def run_ddp_bench(args) -> dict:
         "scaling": "weak",
         "vs_baseline": None,
         "dtype": "bf16",
+        "linear_dtype": cfg.linear_dtype,
         "data": "synthetic (uniform random token ids), random-init weights",
         "config": {"model": model_name, "global_batch": world * mb, "seq_len": seq,
                    "parallelism": f"dp{world}" + ("+zero1" if ddp.sharded else "")},
@@ -243,6 +256,9 @@ def main(argv=None) -> int:
                    help="replicate the optimizer (all-reduce) instead of ZeRO-1 sharding")
     p.add_argument("--grad-reduce", choices=["bf16", "fp32"], default="bf16",
                    help="gradient wire format of the reduce-scatter / all-reduce")
+    p.add_argument("--linear-dtype", choices=["bf16", "mxfp8"], default=None,
+                   help="products of wqkv / wo / w13 / w2: bf16 kernels (default) or the MXFP8 "
+                        "GEMM; unset, the environment variable MXK_LINEAR_DTYPE decides")
     a = p.parse_args(argv)
     out = run_ddp_bench(a)
     if mxdist.world_info()[1] == 0:

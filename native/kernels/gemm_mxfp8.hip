@@ -2,6 +2,8 @@
 // and block-scaled MFMA GEMM for gfx950.
 //
 //   mxk_quantize_mxfp8   bf16 rows -> e4m3 bytes + E8M0 scale bytes
+//   mxk_quantize_mxfp8_t     the same of x^T (blocks of 32 rows), stored transposed
+//   mxk_quantize_mxfp8_dual  both images from one read of x
 //   mxk_gemm_mxfp8_tn    C[M][N] = dequant(A) . dequant(B)^T, fp32
 //                        accumulation, bf16 output; both operands K-contiguous
 //
@@ -86,6 +88,34 @@ __host__ __device__ inline int mx_block_exp(float amax) {
   return e < -127 ? -127 : e;                           // bf16 input: e <= 119
 }
 
+// 8 consecutive elements of an MX block (4 dwords of two bf16 each, memory
+// order) whose other 24 are in the lane's DPP quad: the 8 e4m3 bytes in
+// memory order; returns the block's exponent.  Every lane of the quad must be
+// active.
+__device__ __forceinline__ int quantize_quarter(const uint32_t (&w)[4], uint32_t (&out)[2]) {
+  float f[8];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    f[2 * i] = __uint_as_float(w[i] << 16);
+    f[2 * i + 1] = __uint_as_float(w[i] & 0xFFFF0000u);
+  }
+  float amax = 0.f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) amax = fmaxf(amax, fabsf(f[i]));
+  // the block's other three lanes: quad_perm [1,0,3,2] then [2,3,0,1]
+  amax = fmaxf(amax, __uint_as_float(__builtin_amdgcn_mov_dpp(__float_as_uint(amax), 0xB1, 0xF, 0xF, true)));
+  amax = fmaxf(amax, __uint_as_float(__builtin_amdgcn_mov_dpp(__float_as_uint(amax), 0x4E, 0xF, 0xF, true)));
+  const int e = mx_block_exp(amax);
+  const float inv = __uint_as_float(static_cast<uint32_t>(127 - e) << 23);   // 2^-e
+  out[0] = out[1] = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const float v = fminf(fmaxf(f[i] * inv, -448.f), 448.f);   // explicit saturation
+    out[i >> 2] |= f32_to_e4m3(v) << (8 * (i & 3));
+  }
+  return e;
+}
+
 // One lane per 8 consecutive elements, 4 lanes (a DPP quad) per MX block.
 template <bool VEC>
 __global__ void __launch_bounds__(256)
@@ -106,26 +136,8 @@ quantize_mxfp8_kernel(const uint16_t* __restrict__ x, uint8_t* __restrict__ q,
 #pragma unroll
     for (int i = 0; i < 4; ++i) w[i] = xp[2 * i] | (static_cast<uint32_t>(xp[2 * i + 1]) << 16);
   }
-  float f[8];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    f[2 * i] = __uint_as_float(w[i] << 16);
-    f[2 * i + 1] = __uint_as_float(w[i] & 0xFFFF0000u);
-  }
-  float amax = 0.f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) amax = fmaxf(amax, fabsf(f[i]));
-  // the block's other three lanes: quad_perm [1,0,3,2] then [2,3,0,1]
-  amax = fmaxf(amax, __uint_as_float(__builtin_amdgcn_mov_dpp(__float_as_uint(amax), 0xB1, 0xF, 0xF, true)));
-  amax = fmaxf(amax, __uint_as_float(__builtin_amdgcn_mov_dpp(__float_as_uint(amax), 0x4E, 0xF, 0xF, true)));
-  const int e = mx_block_exp(amax);
-  const float inv = __uint_as_float(static_cast<uint32_t>(127 - e) << 23);   // 2^-e
-  uint32_t out[2] = {0, 0};
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const float v = fminf(fmaxf(f[i] * inv, -448.f), 448.f);   // explicit saturation
-    out[i >> 2] |= f32_to_e4m3(v) << (8 * (i & 3));
-  }
+  uint32_t out[2];
+  const int e = quantize_quarter(w, out);
   uint8_t* qp = q + row * ldq + c8 * 8;
   if constexpr (VEC) {
     *reinterpret_cast<uint2*>(qp) = make_uint2(out[0], out[1]);
@@ -134,6 +146,111 @@ quantize_mxfp8_kernel(const uint16_t* __restrict__ x, uint8_t* __restrict__ q,
     for (int i = 0; i < 8; ++i) qp[i] = static_cast<uint8_t>(out[i >> 2] >> (8 * (i & 3)));
   }
   if ((c8 & 3) == 0) s[row * lds + (c8 >> 2)] = static_cast<uint8_t>(e + 127);
+}
+
+// ---- transposing quantiser ----------------------------------------------------
+// qt[c][r], st[c][r / 32]: the MX blocks are 32 consecutive ROWS of x.  A
+// workgroup takes a 128-row x 64-column tile of x:
+//   load   lane = (row pair, 8-column chunk): two 16-B row accesses (rows r and
+//          r + 1), per wave instruction 8 row pairs x 128 B.  DUAL: the two
+//          rows are also quantised along the row (the chunks of a 32-column
+//          block sit in one DPP quad) and stored, the image of
+//          quantize_mxfp8_kernel.
+//   LDS    transposed image T[c][r] of bf16: x[r][c], x[r + 1][c] go out as one
+//          dword.  A T row is 256 B + 8 B of padding (66 dwords).  A 32-lane
+//          store group holds chunks k = 0..3 (or 4..7) of 8 row pairs: dword
+//          bank (mod 32) 16 (k & 1) + 2 j + pair, 2-way, which a 4-B LDS store
+//          hides.  Unpadded, the 8 (or 4) chunks of a group would meet on one
+//          bank per row pair.  A column read is 16 B per lane at an 8-B aligned
+//          address (one ds_read2_b64): 16 lanes read 256 contiguous bytes of
+//          one T row, 2-way on the 32 banks that instruction has; 4 reads per
+//          lane against 16 stored dwords.
+//   store  lane = (column, 8 rows): amax over the quad that shares the block,
+//          8 contiguous bytes of qt per lane, 128 B per column and tile.
+// Rows >= R and columns >= C of a ragged tile load zeros and store nothing.
+constexpr int kTrRows = 128, kTrCols = 64;
+constexpr int kTrLdsRow = kTrRows * 2 + 8;   // bytes
+
+template <bool VEC, bool DUAL>
+__global__ void __launch_bounds__(256)
+quantize_mxfp8_tr_kernel(const uint16_t* __restrict__ x, uint8_t* __restrict__ q,
+                         uint8_t* __restrict__ s, uint8_t* __restrict__ qt, uint8_t* __restrict__ st,
+                         long R, long C, long ldx, long ldq, long lds, long ldqt, long ldst) {
+  __shared__ __attribute__((aligned(8))) char tile[kTrCols * kTrLdsRow];
+  const int t = threadIdx.x;
+  const int lane = t & 63, wave = t >> 6;
+  const long r0 = static_cast<long>(blockIdx.x) * kTrRows;
+  const long c0 = static_cast<long>(blockIdx.y) * kTrCols;
+  const int k = (lane & 3) | ((lane >> 5) << 2);   // 8-column chunk
+  const int pair = (lane >> 2) & 7;
+  const long col = c0 + k * 8;
+#pragma unroll
+  for (int pass = 0; pass < 2; ++pass) {
+    const int rl = pass * 64 + wave * 16 + pair * 2;   // even row inside the tile
+    uint32_t w[2][4];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const long row = r0 + rl + h;
+      const uint16_t* xp = x + row * ldx + col;
+      if constexpr (VEC) {
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (row < R && col < C) v = *reinterpret_cast<const uint4*>(xp);   // C % 8 == 0
+        w[h][0] = v.x; w[h][1] = v.y; w[h][2] = v.z; w[h][3] = v.w;
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const uint32_t lo = (row < R && col + 2 * i < C) ? xp[2 * i] : 0u;
+          const uint32_t hi = (row < R && col + 2 * i + 1 < C) ? xp[2 * i + 1] : 0u;
+          w[h][i] = lo | (hi << 16);
+        }
+      }
+      if constexpr (DUAL) {
+        uint32_t out[2];
+        const int e = quantize_quarter(w[h], out);
+        if (row < R && col < C) {   // C % 32 == 0: whole blocks
+          uint8_t* qp = q + row * ldq + col;
+          if constexpr (VEC) {
+            *reinterpret_cast<uint2*>(qp) = make_uint2(out[0], out[1]);
+          } else {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) qp[i] = static_cast<uint8_t>(out[i >> 2] >> (8 * (i & 3)));
+          }
+          if ((k & 3) == 0) s[row * lds + (col >> 5)] = static_cast<uint8_t>(e + 127);
+        }
+      }
+    }
+    char* tp = tile + (k * 8) * kTrLdsRow + rl * 2;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      *reinterpret_cast<uint32_t*>(tp + (2 * i) * kTrLdsRow) = (w[0][i] & 0xFFFFu) | (w[1][i] << 16);
+      *reinterpret_cast<uint32_t*>(tp + (2 * i + 1) * kTrLdsRow) =
+          (w[0][i] >> 16) | (w[1][i] & 0xFFFF0000u);
+    }
+  }
+  __syncthreads();
+  const int r8 = t & 15;
+  const long row = r0 + r8 * 8;
+#pragma unroll
+  for (int pass = 0; pass < 4; ++pass) {
+    const int cl = pass * 16 + (t >> 4);
+    const char* tp = tile + cl * kTrLdsRow + r8 * 16;
+    const uint2 a = *reinterpret_cast<const uint2*>(tp);
+    const uint2 b = *reinterpret_cast<const uint2*>(tp + 8);
+    const uint32_t w[4] = {a.x, a.y, b.x, b.y};
+    uint32_t out[2];
+    const int e = quantize_quarter(w, out);
+    const long c = c0 + cl;
+    if (row < R && c < C) {   // R % 32 == 0: whole blocks
+      uint8_t* qp = qt + c * ldqt + row;
+      if constexpr (VEC) {
+        *reinterpret_cast<uint2*>(qp) = make_uint2(out[0], out[1]);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) qp[i] = static_cast<uint8_t>(out[i >> 2] >> (8 * (i & 3)));
+      }
+      if ((r8 & 3) == 0) st[c * ldst + (row >> 5)] = static_cast<uint8_t>(e + 127);
+    }
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -464,4 +581,52 @@ MXK_API int mxk_quantize_mxfp8(const void* x, void* q, void* s, long R, int K, l
                        stream, static_cast<const uint16_t*>(x), static_cast<uint8_t*>(q),
                        static_cast<uint8_t*>(s), R, K, ldx, ldq, lds);
   MXK_RETURN_LAUNCH_STATUS();
+}
+
+namespace {
+
+int launch_quantize_tr(bool dual, const void* x, void* q, void* s, void* qt, void* st, long R, long C,
+                       long ldx, long ldq, long lds, long ldqt, long ldst, hipStream_t stream) {
+  if (!x || !qt || !st || R <= 0 || C <= 0 || R % 32 || ldx < C || ldqt < R || ldst < R / 32)
+    return static_cast<int>(hipErrorInvalidValue);
+  if (dual && (!q || !s || C % 32 || ldq < C || lds < C / 32))
+    return static_cast<int>(hipErrorInvalidValue);
+  const long gx = (R + kTrRows - 1) / kTrRows, gy = (C + kTrCols - 1) / kTrCols;
+  if (gx > 0x7FFFFFFFL || gy > 65535) return static_cast<int>(hipErrorInvalidValue);
+  // 16-B row accesses of x, 8-B stores of qt (and q): everything else goes by element
+  const bool vec = aligned(x, 16) && ldx % 8 == 0 && C % 8 == 0 && aligned(qt, 8) && ldqt % 8 == 0 &&
+                   (!dual || (aligned(q, 8) && ldq % 8 == 0));
+  const dim3 grid(static_cast<unsigned>(gx), static_cast<unsigned>(gy));
+  auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, static_cast<const uint16_t*>(x),
+                       static_cast<uint8_t*>(q), static_cast<uint8_t*>(s), static_cast<uint8_t*>(qt),
+                       static_cast<uint8_t*>(st), R, C, ldx, ldq, lds, ldqt, ldst);
+  };
+  if (dual) {
+    if (vec) go(quantize_mxfp8_tr_kernel<true, true>);
+    else go(quantize_mxfp8_tr_kernel<false, true>);
+  } else {
+    if (vec) go(quantize_mxfp8_tr_kernel<true, false>);
+    else go(quantize_mxfp8_tr_kernel<false, false>);
+  }
+  MXK_RETURN_LAUNCH_STATUS();
+}
+
+}  // namespace
+
+// x: bf16 [R][C] (row stride ldx elements), R % 32 == 0, finite values only.
+// qt: e4m3 bytes [C][R] (row stride ldqt), st: E8M0 bytes [C][R / 32] (row
+// stride ldst): mxk_quantize_mxfp8 of x^T, the MX blocks being 32 consecutive
+// rows of x.  Nothing outside the [C][R] and [C][R / 32] extents is written.
+MXK_API int mxk_quantize_mxfp8_t(const void* x, void* qt, void* st, long R, long C, long ldx,
+                                 long ldqt, long ldst, hipStream_t stream) {
+  return launch_quantize_tr(false, x, nullptr, nullptr, qt, st, R, C, ldx, 0, 0, ldqt, ldst, stream);
+}
+
+// q / s: the image mxk_quantize_mxfp8 writes (C % 32 == 0 as well); qt / st:
+// that of mxk_quantize_mxfp8_t; x is read once.
+MXK_API int mxk_quantize_mxfp8_dual(const void* x, void* q, void* s, void* qt, void* st, long R,
+                                    long C, long ldx, long ldq, long lds, long ldqt, long ldst,
+                                    hipStream_t stream) {
+  return launch_quantize_tr(true, x, q, s, qt, st, R, C, ldx, ldq, lds, ldqt, ldst, stream);
 }
