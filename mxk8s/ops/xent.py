@@ -5,6 +5,8 @@ label >= 0 of ``logsumexp(logits) - logits[label]``, computed in fp32 inside
 the kernel without an fp32 copy of the logits; the backward writes the bf16
 gradient over the logits in place.  CPU / non-bf16 inputs use
 ``torch.nn.functional.cross_entropy`` (the reference the tests compare to).
+Contract: every label is negative (ignored) or below V; the kernel reads
+``logits[row, label]`` unchecked, so a label >= V reads out of bounds.
 """
 from __future__ import annotations
 

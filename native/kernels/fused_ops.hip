@@ -399,11 +399,13 @@ MXK_API int mxk_rmsnorm_bwd(const void* dy, const void* x, const void* w, const 
                             const void* dres, void* dx, void* dw_bf16, float* dw_f32,
                             float* workspace, int rows, int H, hipStream_t s) {
   if (rows <= 0) return 0;
-  if (H % 8 || H > 8 * kChunk || !aligned16(dy) || !aligned16(x) || !aligned16(dx) ||
-      (dres && !aligned16(dres)))
+  // w too: both kernels read it 16 B at a time; the general kernel stores its
+  // dw slab rows as float4
+  if (H % 8 || H > 8 * kChunk || !aligned16(dy) || !aligned16(x) || !aligned16(w) ||
+      !aligned16(dx) || (dres && !aligned16(dres)) || !aligned16(workspace))
     return static_cast<int>(hipErrorInvalidValue);
   const int nb = rows < kBwdBlocks ? rows : kBwdBlocks;
-  if ((H == 2048 || H == 4096 || H == 8192) && aligned16(w) && rows >= 4 * nb) {
+  if ((H == 2048 || H == 4096 || H == 8192) && rows >= 4 * nb) {
     auto* a = static_cast<const uint16_t*>(dy);
     auto* b = static_cast<const uint16_t*>(x);
     auto* g = static_cast<const uint16_t*>(w);

@@ -1,0 +1,150 @@
+"""The fp64 closed forms in ``tests/kernel_refs.py`` against ``torch.autograd``
+(and ``torch.optim.AdamW``) in float64: the GPU numerics tests compare the HIP
+kernels with these forms, so a wrong form must not be able to hide a wrong
+kernel.  Tolerance 1e-12 relative to ``mag`` (fp64 round-off is 1.1e-16 per
+operation; the forms are a handful of operations and sums of at most 64
+terms)."""
+import pytest
+import torch
+import torch.nn.functional as F
+
+import kernel_refs as R
+
+RTOL = 1e-12
+
+
+def _r(shape, seed):
+    return torch.randn(shape, dtype=torch.float64, generator=torch.Generator().manual_seed(seed))
+
+
+def _close(got, ref, mag, what):
+    ratio = ((got - ref).abs() / (RTOL * mag + 1e-300)).max().item()
+    assert ratio <= 1, f"{what}: error / bound = {ratio:.3g}"
+    assert (mag >= ref.abs() * (1 - 1e-12)).all(), f"{what}: mag below |ref|"
+
+
+@pytest.mark.parametrize("rows,H", [(1, 8), (5, 24), (7, 64)])
+@pytest.mark.parametrize("with_res", [False, True])
+def test_rmsnorm_forms(rows, H, with_res):
+    eps = 1e-5
+    x = _r((rows, H), 1) * (2.0 ** (torch.arange(rows) % 5 - 2))[:, None].double()
+    if rows > 2:
+        x[1] = 0           # rstd = eps^-1/2
+        x[2] *= 2.0 ** -10  # eps decides
+    w, dy, dres = _r(H, 2), _r((rows, H), 3), _r((rows, H), 4)
+    xa, wa = x.clone().requires_grad_(), w.clone().requires_grad_()
+    ya = xa * torch.rsqrt(xa.pow(2).mean(-1, keepdim=True) + eps) * wa
+    y, rs, mag_y = R.rmsnorm_fwd(x, w, eps)
+    _close(y, ya.detach(), mag_y, "y")
+    _close(rs, torch.rsqrt(x.pow(2).mean(-1) + eps), rs, "rstd")
+    if rows > 2:
+        assert rs[1].item() == pytest.approx(eps ** -0.5, rel=1e-14)
+    # the residual stream is an identity branch beside the norm: its gradient
+    # dres adds to dx
+    outs, grads = ([ya, xa * 1.0], [dy, dres]) if with_res else ([ya], [dy])
+    gx, gw = torch.autograd.grad(outs, [xa, wa], grads)
+    dx, mag_dx, dw, mag_dw = R.rmsnorm_bwd(dy, x, w, eps, dres if with_res else None)
+    _close(dx, gx, mag_dx, "dx")
+    _close(dw, gw, mag_dw, "dw")
+
+
+@pytest.mark.parametrize("rows,Fd", [(1, 8), (3, 40)])
+def test_swiglu_forms(rows, Fd):
+    g = _r((rows, Fd), 5) * 3
+    special = torch.tensor([0.0, -0.0, 2.0 ** -20, -2.0 ** -20, -1.278, 20, -20, 88, -88, 200, -200],
+                           dtype=torch.float64)
+    g.view(-1)[:min(g.numel(), special.numel())] = special[:g.numel()]
+    u, dh = _r((rows, Fd), 6), _r((rows, Fd), 7)
+    ga, ua = g.clone().requires_grad_(), u.clone().requires_grad_()
+    ha = F.silu(ga) * ua
+    gg, gu = torch.autograd.grad(ha, [ga, ua], dh)
+    h, mag_h = R.swiglu_fwd(g, u)
+    _close(h, ha.detach(), mag_h, "h")
+    dg, mag_dg, du, mag_du = R.swiglu_bwd(g, u, dh)
+    _close(dg, gg, mag_dg, "dg")
+    _close(du, gu, mag_du, "du")
+    assert torch.isfinite(dg).all() and torch.isfinite(du).all()
+
+
+@pytest.mark.parametrize("B,S,heads,D", [(1, 1, 1, 16), (2, 5, 3, 32)])
+def test_rope_forms(B, S, heads, D):
+    x = _r((B * S, heads, D), 8)
+    ang = _r((S, D // 2), 9) * 3
+    cos, sin = ang.cos(), ang.sin()
+    # complex form: (a + i b) (c + i sign s), position t mod S
+    pos = torch.arange(B * S) % S
+    z = torch.complex(x[..., :D // 2], x[..., D // 2:])
+    for sign in (1.0, -1.0):
+        rot = torch.complex(cos[pos], sign * sin[pos])[:, None, :]
+        zr = z * rot
+        y, mag = R.rope(x, cos, sin, sign, S)
+        _close(y, torch.cat([zr.real, zr.imag], -1), mag, f"rope sign {sign}")
+    # sign -1 is the backward (transpose) of sign +1
+    xa = x.clone().requires_grad_()
+    c, s = cos[pos][:, None, :], sin[pos][:, None, :]
+    a, b = xa[..., :D // 2], xa[..., D // 2:]
+    ya = torch.cat([a * c - b * s, b * c + a * s], -1)
+    dy = _r(x.shape, 10)
+    (gx,) = torch.autograd.grad(ya, xa, dy)
+    back, mag = R.rope(dy, cos, sin, -1.0, S)
+    _close(back, gx, mag, "rope backward")
+    # distinct table rows give distinct outputs for the same input vector
+    if S > 1:
+        same = torch.ones((S, 1, D), dtype=torch.float64)
+        ys, _ = R.rope(same, cos, sin, 1.0, S)
+        assert len({tuple(r.flatten().tolist()) for r in ys}) == S
+
+
+@pytest.mark.parametrize("T,V", [(3, 8), (6, 40)])
+def test_xent_forms(T, V):
+    x = _r((T, V), 11) * 3
+    labels = torch.arange(T) * 7 % V
+    labels[-1] = -100
+    labels[0] = V - 1
+    if T > 3:
+        x[1, :8] = float("-inf")          # masked run, label elsewhere
+        labels[1] = 9
+        x[2] = torch.linspace(-60, 60, V, dtype=torch.float64)
+        x[3, labels[3]] = 40.0            # p ~ 1
+    g = 0.37
+    xa = x.clone().requires_grad_()
+    rows = F.cross_entropy(xa, labels, ignore_index=-100, reduction="none")
+    (gx,) = torch.autograd.grad(rows.sum() * g, xa)
+    lse, loss, dl, mag = R.xent(x, labels, g)
+    _close(lse, torch.logsumexp(x, -1), lse.abs(), "lse")
+    _close(loss, rows.detach(), lse.abs() + 60, "row loss")
+    _close(dl, gx, mag, "dlogits")
+    assert loss[-1].item() == 0 and not dl[-1].any()
+    assert torch.isfinite(dl).all() and torch.isfinite(loss).all()
+    # mean over counted rows, the wrapper's reduction
+    mean = F.cross_entropy(x, labels, ignore_index=-100)
+    assert (loss.sum() / (labels >= 0).sum()).item() == pytest.approx(mean.item(), rel=1e-13)
+
+
+@pytest.mark.parametrize("step", [1, 2, 1000])
+@pytest.mark.parametrize("wd", [0.0, 0.1])
+@pytest.mark.parametrize("scale", [1.0, 0.25])
+def test_adamw_form_vs_torch_optim(step, wd, scale):
+    n = 37
+    lr, b1, b2, eps = 1e-3, 0.9, 0.999, 1e-8
+    p, m, v, grad = _r(n, 12), _r(n, 13) * 0.1, (_r(n, 14) * 0.1).pow(2), _r(n, 15)
+    par = torch.nn.Parameter(p.clone())
+    opt = torch.optim.AdamW([par], lr=lr, betas=(b1, b2), eps=eps, weight_decay=wd)
+    opt.state[par] = {"step": torch.tensor(float(step - 1)), "exp_avg": m.clone(),
+                      "exp_avg_sq": v.clone()}
+    par.grad = grad * scale
+    opt.step()
+    st = opt.state[par]
+    assert int(st["step"].item()) == step
+    p1, m1, v1, mag_p, mag_m, mag_v = R.adamw_step(p, m, v, grad, lr, b1, b2, eps, wd, step, scale)
+    _close(m1, st["exp_avg"], mag_m, "exp_avg")
+    _close(v1, st["exp_avg_sq"], mag_v, "exp_avg_sq")
+    _close(p1, par.detach(), mag_p, "param")
+
+
+def test_ratio_helper_flags_nan_and_scales():
+    ref = torch.tensor([1.0, 2.0], dtype=torch.float64)
+    assert R.max_ratio(ref.clone(), ref, ref.abs(), 2.0 ** -8, 1e-30) == 0
+    assert R.max_ratio(ref * (1 + 2.0 ** -8), ref, ref.abs(), 2.0 ** -8, 0.0) == pytest.approx(1.0)
+    assert not R.max_ratio(torch.tensor([1.0, float("nan")]), ref, ref.abs(), 1.0, 1.0) <= 1
+    assert R.f32(0.999) == 0.9990000128746033
