@@ -11,6 +11,7 @@
 #   make test-native  host unit tests of libmxnode (ASan+UBSan build)
 #   make test-native-tsan  libmxnode re-entrancy test under ThreadSanitizer
 #   make test-attention-plan  the attention backward plan's sweep (host, ASan+UBSan build)
+#   make test-attention-doc   the document-mask predicate and tile bounds (host, ASan+UBSan build)
 #
 # Everything lands inside the repo so `gpurun` snapshots carry it to the box.
 
@@ -40,7 +41,7 @@ NODE_SRCS := $(wildcard native/libmxnode/*.cc)
 NODE_OBJS := $(patsubst native/libmxnode/%.cc,$(BUILD)/node/%.o,$(NODE_SRCS))
 NODE_HDRS := $(wildcard native/libmxnode/*.h)
 
-.PHONY: all kernels gemm-exp node tools clean test-native test-native-tsan test-attention-plan fake-amdsmi
+.PHONY: all kernels gemm-exp node tools clean test-native test-native-tsan test-attention-plan test-attention-doc fake-amdsmi
 all: kernels node tools fake-amdsmi
 
 kernels: $(OUT_LIB)/libmxkernels.so
@@ -139,6 +140,14 @@ test-attention-plan: $(BUILD)/asan/attention_plan_sweep
 	$<
 
 $(BUILD)/asan/attention_plan_sweep: native/kernels/tests/attention_plan_sweep.cc native/kernels/attention_plan.h
+	@mkdir -p $(dir $@)
+	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -Wshadow -fsanitize=address,undefined -fno-sanitize-recover=all \
+	    -fno-omit-frame-pointer -Inative/kernels -o $@ $<
+
+test-attention-doc: $(BUILD)/asan/attention_doc_sweep
+	$<
+
+$(BUILD)/asan/attention_doc_sweep: native/kernels/tests/attention_doc_sweep.cc native/kernels/attention_plan.h
 	@mkdir -p $(dir $@)
 	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -Wshadow -fsanitize=address,undefined -fno-sanitize-recover=all \
 	    -fno-omit-frame-pointer -Inative/kernels -o $@ $<

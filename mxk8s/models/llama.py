@@ -77,10 +77,15 @@ class LlamaConfig:
         per_layer = d * (d + 2 * kv) + d * d + 3 * d * f + 2 * d
         return L * per_layer + 2 * v * d + d
 
-    def flops_per_token(self, seq_len: int) -> float:
-        """Training FLOPs/token: 6 * params (matmuls) + attention (causal)."""
+    def flops_per_token(self, seq_len: int, attn_fraction: float | None = None) -> float:
+        """Training FLOPs/token: 6 * params (matmuls) + attention (causal).
+        ``attn_fraction``: the share of the causal (query, key) pairs a
+        document mask leaves visible (``DocMask.visible_fraction``), which
+        scales the attention term; None is the causal count."""
         n = self.num_params() - self.vocab_size * self.dim   # embedding lookup is free
         attn = 6 * self.n_layers * self.dim * seq_len       # 12*L*d*S, halved by causality
+        if attn_fraction is not None:
+            attn = attn * float(attn_fraction)
         return 6.0 * n + attn
 
 
@@ -105,10 +110,21 @@ class Attention(nn.Module):
         self.wqkv = Linear(cfg.dim, (cfg.n_heads + 2 * cfg.n_kv_heads) * hd, compute=cfg.linear_dtype)
         self.wo = Linear(cfg.n_heads * hd, cfg.dim, compute=cfg.linear_dtype)
 
-    def forward(self, x, cos, sin):
+    def forward(self, x, cos, sin, doc=None):
         B, S, _ = x.shape
         c = self.cfg
         hd = c.head_dim
+        if doc is not None:
+            # packed rows (a DocMask): causal within a document.  The fused
+            # RoPE nodes have no masked form: qkv_rope + the DOC kernels
+            q, k, v = qkv_rope(self.wqkv(x), cos, sin, c.n_heads, c.n_kv_heads, hd)
+            if flash_supported(q, k, v):
+                o = flash_attention(q, k, v, causal=True, doc=doc)
+                return self.wo(o.reshape(B, S, c.n_heads * hd))
+            o = F.scaled_dot_product_attention(q.transpose(1, 2), k.transpose(1, 2),
+                                               v.transpose(1, 2), attn_mask=doc.bool_mask()[:, None],
+                                               enable_gqa=True)
+            return self.wo(o.transpose(1, 2).reshape(B, S, c.n_heads * hd))
         # projection + RoPE (in the GEMM's epilogue) + flash attention as one
         # node; its backward takes d(qkv) from the attention kernels with the
         # RoPE backward fused into their stores (a bf16 GEMM: not with mxfp8 linears)
@@ -165,8 +181,8 @@ class Block(nn.Module):
         self.mlp_norm = RMSNorm(cfg.dim, cfg.norm_eps)
         self.mlp = MLP(cfg)
 
-    def forward(self, h, y, cos, sin):
-        a = self.attn(y, cos, sin)
+    def forward(self, h, y, cos, sin, doc=None):
+        a = self.attn(y, cos, sin, doc) if doc is not None else self.attn(y, cos, sin)
         h, y2 = add_rmsnorm(h, a, self.mlp_norm.weight, self.mlp_norm.eps)
         return h, self.mlp(y2)
 
@@ -209,22 +225,29 @@ class Llama(nn.Module):
                                           self.cfg.rope_theta, device=device)
         return self._rope[key]
 
-    def forward(self, tokens: torch.Tensor) -> torch.Tensor:
+    def forward(self, tokens: torch.Tensor, doc=None) -> torch.Tensor:
+        """``doc``: a ``mxk8s.ops.attention.DocMask`` of ``tokens``' [B, S] on
+        their device - attention is then causal within a document."""
+        if doc is not None and (doc.shape != tuple(tokens.shape) or doc.device != tokens.device):
+            raise ValueError(f"doc is {doc.shape} on {doc.device}, tokens are "
+                             f"{tuple(tokens.shape)} on {tokens.device}")
         cos, sin = self.rope_tables(tokens.device)
         h = self.embed(tokens)
         y = rmsnorm(h, self.layers[0].attn_norm.weight, self.cfg.norm_eps) if self.layers else h
         for i, layer in enumerate(self.layers):
-            h, delta = layer(h, y, cos, sin)
+            h, delta = layer(h, y, cos, sin, doc) if doc is not None else layer(h, y, cos, sin)
             nxt = self.layers[i + 1].attn_norm if i + 1 < len(self.layers) else self.norm
             h, y = add_rmsnorm(h, delta, nxt.weight, nxt.eps)
         return self.lm_head(y)
 
-    def loss(self, tokens: torch.Tensor, labels: torch.Tensor | None = None) -> torch.Tensor:
-        """Next-token cross entropy (fp32 softmax)."""
+    def loss(self, tokens: torch.Tensor, labels: torch.Tensor | None = None,
+             doc=None) -> torch.Tensor:
+        """Next-token cross entropy (fp32 softmax).  ``doc`` (a ``DocMask``)
+        describes the input columns: ``tokens[:, :-1]`` without labels."""
         if labels is None:
             inp, labels = tokens[:, :-1], tokens[:, 1:]
         else:
             inp = tokens
-        logits = self(inp)
+        logits = self(inp) if doc is None else self(inp, doc)
         # fused bf16 softmax cross-entropy on GPU (no fp32 logits copy)
         return cross_entropy(logits.reshape(-1, logits.shape[-1]), labels.reshape(-1))

@@ -99,6 +99,10 @@ _SIGNATURES = {
     "mxk_gemm_bf16_rope": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp]),
     "mxk_attn_bwd_rope": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i,
                                _l, _l, _l, _l, _l, _l, _vp, _vp, _f, _i, _vp]),
+    "mxk_attn_fwd_doc": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _l, _l, _l, _f, _vp]),
+    "mxk_attn_bwd_doc_workspace": (_l, [_i, _i, _i]),
+    "mxk_attn_bwd_doc": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i,
+                              _i, _i, _l, _l, _l, _l, _l, _f, _vp]),
     "mxk_attn_bwd_plan": (_i, [_i, _i, _i, _i, _l, _l, _l, _l, _l, _i, _i,
                                ctypes.POINTER(ctypes.c_long)]),
     "mxk_xent_fwd": (_i, [_vp, _vp, _vp, _vp, _l, _i, _l, _vp]),

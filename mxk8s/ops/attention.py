@@ -38,11 +38,143 @@ def supported(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> bool:
     return True
 
 
-def attention_ref(q, k, v, causal: bool = True, scale: float | None = None) -> torch.Tensor:
-    """fp32 reference: q [B,S,Hq,D], k/v [B,S,Hkv,D] -> [B,S,Hq,D] (q.dtype)."""
+class DocMask:
+    """Document boundaries of packed rows: attention is causal within a
+    document.  Query ``i`` of batch row ``b`` sees key ``j`` iff
+    ``doc_start[b, i] <= j <= i``; ``doc_start[b, i]`` is the index of the
+    first token of ``i``'s document and ``doc_end[b, j]`` (derived, never
+    supplied) the exclusive end of ``j``'s.  Both are int32 ``[B, S]`` on one
+    device and are not meant to be modified.  Built only through the
+    constructors below, which produce valid tables: ``doc_start[b, 0] == 0``
+    and ``doc_start[b, i]`` is ``doc_start[b, i - 1]`` or ``i``.  Positions
+    are not reset at a boundary (RoPE is relative)."""
+
+    __slots__ = ("doc_start", "doc_end")
+
+    def __init__(self, doc_start: torch.Tensor, doc_end: torch.Tensor, _token=None):
+        if _token is not DocMask:
+            raise TypeError("build a DocMask with from_lengths / from_ids / from_eos / "
+                            "from_doc_start")
+        object.__setattr__(self, "doc_start", doc_start)
+        object.__setattr__(self, "doc_end", doc_end)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("DocMask is immutable")
+
+    @classmethod
+    def _from_first(cls, first: torch.Tensor) -> "DocMask":
+        """``first`` bool [B, S]: token i opens a document (column 0 always does)."""
+        first = first.clone()
+        first[:, 0] = True
+        B, S = first.shape
+        idx = torch.arange(S, device=first.device).expand(B, S)
+        start = torch.where(first, idx, idx.new_zeros(())).cummax(dim=1).values
+        # the end of i's document: the next opening after i, or S
+        nxt = torch.where(first, idx, idx.new_full((), S))
+        nxt = torch.cat([nxt[:, 1:], nxt.new_full((B, 1), S)], dim=1)
+        end = nxt.flip(1).cummin(dim=1).values.flip(1)
+        return cls(start.to(torch.int32).contiguous(), end.to(torch.int32).contiguous(),
+                   _token=cls)
+
+    @classmethod
+    def from_lengths(cls, lengths, S: int, device=None) -> "DocMask":
+        """``lengths``: per batch row, the list of its document lengths (each >= 1, summing to S)."""
+        first = torch.zeros((len(lengths), S), dtype=torch.bool)
+        for b, row in enumerate(lengths):
+            row = [int(n) for n in row]
+            if not row or min(row) < 1 or sum(row) != S:
+                raise ValueError(f"document lengths of row {b} must be >= 1 and sum to {S}: {row}")
+            pos = 0
+            for n in row:
+                first[b, pos] = True
+                pos += n
+        m = cls._from_first(first)
+        return m.to(device) if device is not None else m
+
+    @classmethod
+    def from_ids(cls, doc_ids: torch.Tensor) -> "DocMask":
+        """``doc_ids`` integer [B, S]: a boundary is where the id changes."""
+        if doc_ids.dim() != 2 or doc_ids.shape[1] < 1:
+            raise ValueError(f"doc_ids must be [B, S], got {tuple(doc_ids.shape)}")
+        first = torch.ones_like(doc_ids, dtype=torch.bool)
+        first[:, 1:] = doc_ids[:, 1:] != doc_ids[:, :-1]
+        return cls._from_first(first)
+
+    @classmethod
+    def from_eos(cls, tokens: torch.Tensor, eos_id: int) -> "DocMask":
+        """A document ends after each ``eos_id`` of ``tokens`` [B, S]."""
+        if tokens.dim() != 2 or tokens.shape[1] < 1:
+            raise ValueError(f"tokens must be [B, S], got {tuple(tokens.shape)}")
+        first = torch.ones_like(tokens, dtype=torch.bool)
+        first[:, 1:] = tokens[:, :-1] == eos_id
+        return cls._from_first(first)
+
+    @classmethod
+    def from_doc_start(cls, t: torch.Tensor, validate: bool = True) -> "DocMask":
+        """From a ``doc_start`` table [B, S]; ``validate`` checks the validity
+        rule on the host and raises ``ValueError``."""
+        if t.dim() != 2 or t.shape[1] < 1 or t.is_floating_point():
+            raise ValueError(f"doc_start must be an integer [B, S] tensor, got {tuple(t.shape)} "
+                             f"{t.dtype}")
+        idx = torch.arange(t.shape[1], device=t.device).expand_as(t)
+        if validate:
+            h = t.detach().cpu().long()
+            hi = idx.cpu()
+            if bool((h[:, 0] != 0).any()):
+                raise ValueError("doc_start[b, 0] must be 0")
+            ok = (h[:, 1:] == h[:, :-1]) | (h[:, 1:] == hi[:, 1:])
+            if not bool(ok.all()):
+                b, i = (~ok).nonzero()[0].tolist()
+                raise ValueError(f"doc_start[{b}, {i + 1}] = {int(h[b, i + 1])} is neither "
+                                 f"doc_start[{b}, {i}] = {int(h[b, i])} nor {i + 1}")
+        return cls._from_first(t == idx)
+
+    def to(self, device) -> "DocMask":
+        return DocMask(self.doc_start.to(device), self.doc_end.to(device), _token=DocMask)
+
+    @property
+    def shape(self):
+        return tuple(self.doc_start.shape)
+
+    @property
+    def device(self):
+        return self.doc_start.device
+
+    def bool_mask(self) -> torch.Tensor:
+        """[B, S, S] bool, True where query i sees key j."""
+        S = self.doc_start.shape[1]
+        j = torch.arange(S, device=self.device)
+        return (j[None, None, :] >= self.doc_start[:, :, None]) & (j[None, None, :] <= j[None, :, None])
+
+    def visible_fraction(self) -> float:
+        """Visible (query, key) pairs over the causal S (S + 1) / 2, averaged over the rows."""
+        B, S = self.doc_start.shape
+        i = torch.arange(S, device=self.device)
+        pairs = (i[None, :] - self.doc_start.long() + 1).sum().item()
+        return float(pairs) / (B * S * (S + 1) / 2)
+
+
+def _check_doc(doc: DocMask, q: torch.Tensor, causal: bool) -> None:
+    if not isinstance(doc, DocMask):
+        raise TypeError(f"doc must be a DocMask, got {type(doc).__name__}")
+    if not causal:
+        raise ValueError("a document mask is causal within a document: causal=False with doc "
+                         "is not supported")
+    if doc.shape != tuple(q.shape[:2]):
+        raise ValueError(f"doc tables are {doc.shape}, q is [B, S] = {tuple(q.shape[:2])}")
+    if doc.device != q.device:
+        raise ValueError(f"doc is on {doc.device}, q on {q.device}: move it with doc.to(device)")
+
+
+def attention_ref(q, k, v, causal: bool = True, scale: float | None = None,
+                  doc: DocMask | None = None) -> torch.Tensor:
+    """fp32 reference: q [B,S,Hq,D], k/v [B,S,Hkv,D] -> [B,S,Hq,D] (q.dtype).
+    ``doc``: causal within a document (``DocMask``)."""
     B, S, Hq, D = q.shape
     Hkv = k.shape[2]
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    if doc is not None:
+        _check_doc(doc, q, causal)
     qf = q.float().transpose(1, 2)
     kf = k.float().transpose(1, 2).repeat_interleave(Hq // Hkv, dim=1)
     vf = v.float().transpose(1, 2).repeat_interleave(Hq // Hkv, dim=1)
@@ -50,12 +182,18 @@ def attention_ref(q, k, v, causal: bool = True, scale: float | None = None) -> t
     if causal:
         mask = torch.ones(S, S, dtype=torch.bool, device=q.device).triu(1)
         s = s.masked_fill(mask, float("-inf"))
+    if doc is not None:
+        s = s.masked_fill(~doc.bool_mask()[:, None], float("-inf"))
     o = torch.softmax(s, dim=-1) @ vf
     return o.transpose(1, 2).to(q.dtype)
 
 
-def attn_fwd(q, k, v, causal: bool = True, scale: float | None = None, variant: int = 4):
+def attn_fwd(q, k, v, causal: bool = True, scale: float | None = None, variant: int | None = None,
+             doc: DocMask | None = None):
     """HIP forward: returns (o [B,S,Hq,D] bf16, lse [B,Hq,S] fp32).
+
+    ``doc`` (a ``DocMask``): causal within a document, on the DOC form of
+    variant 4 (``mxk_attn_fwd_doc``); it cannot be combined with ``variant``.
 
     ``variant`` 4 (default): K/V by LDS-DMA, software-pipelined body (exp of
     one P chunk under the PV MFMAs of the previous one), lazy rescale (the
@@ -69,6 +207,17 @@ def attn_fwd(q, k, v, causal: bool = True, scale: float | None = None, variant: 
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
     o = torch.empty((B, S, Hq, D), dtype=q.dtype, device=q.device)
     lse = torch.empty((B, Hq, S), dtype=torch.float32, device=q.device)
+    if doc is not None:
+        if variant is not None:
+            raise ValueError("attn_fwd: variant= cannot be combined with doc=")
+        _check_doc(doc, q, causal)
+        st = _lib.lib().mxk_attn_fwd_doc(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
+                                         lse.data_ptr(), doc.doc_start.data_ptr(), B, S, Hq, Hkv, D,
+                                         q.stride(1), k.stride(1), v.stride(1), float(scale),
+                                         _lib.stream_ptr(q.device))
+        _lib.check(st, "mxk_attn_fwd_doc")
+        return o, lse
+    variant = 4 if variant is None else variant
     st = _lib.lib().mxk_attn_fwd_variant(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
                                          lse.data_ptr(), B, S, Hq, Hkv, D, q.stride(1),
                                          k.stride(1), v.stride(1), float(scale), int(causal),
@@ -81,16 +230,20 @@ _BWD_VARIANT = int(os.environ.get("MXK_ATTN_BWD_VARIANT", "9"))
 
 
 def attn_bwd(q, k, v, o, lse, dout, causal: bool = True, scale: float | None = None,
-             dk=None, dv=None, variant: int | None = None):
+             dk=None, dv=None, variant: int | None = None, doc: DocMask | None = None):
     """HIP backward: returns (dq [B,S,Hq,D], dk [B,S,Hkv,D], dv [B,S,Hkv,D]).
 
     ``dk``/``dv`` may be preallocated views (e.g. slices of a fused dQKV
     buffer) with a token stride; by default they are fresh contiguous tensors.
     ``variant`` 0-9, default 9: the variants, their history and how a layout
     one does not take degrades (9 -> 6 -> 5) are listed beside ``AttnBwdPlan``
-    in ``native/kernels/attention_plan.h``."""
+    in ``native/kernels/attention_plan.h``.  ``doc`` (a ``DocMask``): causal
+    within a document, on the DOC forms of variant 5's kernels
+    (``mxk_attn_bwd_doc``); it cannot be combined with ``variant``."""
     B, S, Hq, D = q.shape
     Hkv = k.shape[2]
+    if doc is not None and variant is not None:
+        raise ValueError("attn_bwd: variant= cannot be combined with doc=")
     variant = _BWD_VARIANT if variant is None else variant
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
     dout = dout.contiguous()
@@ -100,6 +253,18 @@ def attn_bwd(q, k, v, o, lse, dout, causal: bool = True, scale: float | None = N
     if dv is None:
         dv = torch.empty((B, S, Hkv, D), dtype=v.dtype, device=v.device)
     L = _lib.lib()
+    if doc is not None:
+        _check_doc(doc, q, causal)
+        ws = torch.empty(L.mxk_attn_bwd_doc_workspace(B, S, Hq) // 4, dtype=torch.float32,
+                         device=q.device)
+        st = L.mxk_attn_bwd_doc(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
+                                dout.data_ptr(), lse.data_ptr(), dq.data_ptr(), dk.data_ptr(),
+                                dv.data_ptr(), ws.data_ptr(), doc.doc_start.data_ptr(),
+                                doc.doc_end.data_ptr(), B, S, Hq, Hkv, D, q.stride(1), k.stride(1),
+                                v.stride(1), dk.stride(1), dv.stride(1), float(scale),
+                                _lib.stream_ptr(q.device))
+        _lib.check(st, "mxk_attn_bwd_doc")
+        return dq, dk, dv
     ws = torch.empty(L.mxk_attn_bwd_workspace_variant(B, S, Hq, int(variant)) // 4,
                      dtype=torch.float32, device=q.device)
     st = L.mxk_attn_bwd_variant(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
@@ -124,6 +289,23 @@ class _FlashAttention(torch.autograd.Function):
     def backward(ctx, dout):
         q, k, v, o, lse = ctx.saved_tensors
         dq, dk, dv = attn_bwd(q, k, v, o, lse, dout, causal=ctx.causal, scale=ctx.scale)
+        return dq, dk, dv, None, None
+
+
+class _DocFlashAttention(torch.autograd.Function):
+    """Causal-within-a-document attention on the DOC kernels (``DocMask``)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, doc, scale):
+        o, lse = attn_fwd(q, k, v, causal=True, scale=scale, doc=doc)
+        ctx.save_for_backward(q, k, v, o, lse)
+        ctx.doc, ctx.scale = doc, scale
+        return o
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, o, lse = ctx.saved_tensors
+        dq, dk, dv = attn_bwd(q, k, v, o, lse, dout, causal=True, scale=ctx.scale, doc=ctx.doc)
         return dq, dk, dv, None, None
 
 
@@ -289,11 +471,23 @@ def qkv_rope_attention(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, 
                                    hq, hkv, hd, causal, scale)
 
 
-def flash_attention(q, k, v, causal: bool = True, scale: float | None = None) -> torch.Tensor:
+def flash_attention(q, k, v, causal: bool = True, scale: float | None = None,
+                    doc: DocMask | None = None) -> torch.Tensor:
     """Attention o [B,S,Hq,D] for q [B,S,Hq,D], k/v [B,S,Hkv,D] (GQA).
 
     Runs the HIP kernels for supported CUDA bf16 inputs (``supported``);
-    CPU / other dtypes take the fp32 reference (used by the CPU tests)."""
+    CPU / other dtypes take the fp32 reference (used by the CPU tests).
+    ``doc`` (a ``DocMask`` of q's [B, S] on q's device): causal within a
+    document, for packed rows; ``causal=False`` with it is a ``ValueError``."""
+    if doc is not None:
+        _check_doc(doc, q, causal)
+        if supported(q, k, v):
+            return _DocFlashAttention.apply(q, k, v, doc, scale)
+        if q.device.type == "cuda":
+            raise RuntimeError(f"flash_attention: unsupported shape/layout on GPU: q "
+                               f"{tuple(q.shape)} strides {q.stride()} (need head_dim 128, "
+                               f"S % 128 == 0)")
+        return attention_ref(q, k, v, causal=True, scale=scale, doc=doc)
     if supported(q, k, v):
         return _FlashAttention.apply(q, k, v, causal, scale)
     if q.device.type == "cuda":

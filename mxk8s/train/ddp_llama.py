@@ -69,6 +69,47 @@ def resolve_linear_dtype(args) -> str:
     return v
 
 
+def resolve_doc_len(args) -> int:
+    """``--doc-len``, else the environment variable ``MXK_DOC_LEN`` (so
+    ``bench.py --mode ddp`` can be A/B'd unchanged), else 0: off.  A positive
+    value packs each synthetic row with documents of that mean length and
+    masks attention at their boundaries."""
+    v = getattr(args, "doc_len", None)
+    if v is None:
+        v = os.environ.get("MXK_DOC_LEN") or 0
+    v = int(v)
+    if v < 0:
+        raise ValueError(f"doc length must be >= 0, got {v}")
+    return v
+
+
+def synthetic_doc_masks(n: int, batch: int, seq: int, mean_len: int, seed: int):
+    """``n`` DocMasks [batch, seq] (CPU) from one CPU generator: document
+    lengths drawn geometrically with mean ``mean_len``, clipped to [1, seq],
+    the last document of a row truncated at the row's end."""
+    from ..ops.attention import DocMask
+    g = torch.Generator().manual_seed(seed)
+    p = 1.0 / max(1.0, float(mean_len))
+    log1mp = torch.log1p(torch.tensor(-p, dtype=torch.float64)).item() if p < 1.0 else None
+    masks = []
+    for _ in range(n):
+        rows = []
+        for _ in range(batch):
+            lens, left = [], seq
+            while left > 0:
+                if log1mp is None:
+                    k = 1
+                else:
+                    u = torch.rand((), generator=g, dtype=torch.float64).item()
+                    k = int(torch.log1p(torch.tensor(-u, dtype=torch.float64)).item() / log1mp) + 1
+                k = min(max(k, 1), seq, left)
+                lens.append(k)
+                left -= k
+            rows.append(lens)
+        masks.append(DocMask.from_lengths(rows, seq))
+    return masks
+
+
 def build(cfg: LlamaConfig, device: torch.device, bucket_mb: float, lr: float = 3e-4,
           zero: bool = True, overlap: bool | None = None, reduce_dtype: str = "bf16",
           gather_overlap: bool = True):
@@ -113,10 +154,10 @@ def overlap_stages(model: Llama):
     return stages
 
 
-def train_step(model, ddp, opt, tokens) -> torch.Tensor:
+def train_step(model, ddp, opt, tokens, doc=None) -> torch.Tensor:
     # roctx ranges: host-side phases on rocprofv3 --marker-trace timelines
     with roctx.range("step.forward"):
-        loss = model.loss(tokens)
+        loss = model.loss(tokens) if doc is None else model.loss(tokens, doc=doc)
     with roctx.range("step.backward+allreduce"):
         loss.backward()
         ddp.finish_grad_sync()
@@ -166,6 +207,15 @@ def run_ddp_bench(args) -> dict:
     nbatches = 4
     batches = [torch.randint(0, cfg.vocab_size, (mb, seq + 1), device=dev, generator=g)
                for _ in range(nbatches)]
+    # packed rows (opt-in): one seeded document table per batch, built on the
+    # host and moved to the device once
+    doc_len = resolve_doc_len(args)
+    docs = [None] * nbatches
+    doc_info = None
+    if doc_len:
+        docs = [m.to(dev) for m in synthetic_doc_masks(nbatches, mb, seq, doc_len, 2000 + rank)]
+        vis = sum(m.visible_fraction() for m in docs) / nbatches
+        doc_info = {"mean_doc_len": doc_len, "visible_fraction": round(vis, 6)}
 
     def sync():
         if dev.type == "cuda":
@@ -176,7 +226,7 @@ def run_ddp_bench(args) -> dict:
         from . import checkpoint
         start_step = checkpoint.load(args.resume, ddp, opt)
     for i in range(args.warmup):
-        train_step(model, ddp, opt, batches[i % nbatches])
+        train_step(model, ddp, opt, batches[i % nbatches], docs[i % nbatches])
     sync()
     mxdist.barrier()
     sync()
@@ -190,7 +240,8 @@ def run_ddp_bench(args) -> dict:
         # update had just collapsed (0.87 at 2 layers: a memorised batch, not
         # a training signal)
         for i in range(args.steps):
-            losses.append(train_step(model, ddp, opt, batches[(args.warmup + i) % nbatches]))
+            b = (args.warmup + i) % nbatches
+            losses.append(train_step(model, ddp, opt, batches[b], docs[b]))
         sync()
     mxdist.barrier()
     sync()
@@ -202,7 +253,7 @@ def run_ddp_bench(args) -> dict:
                         step=start_step + args.warmup + args.steps)
     tokens = world * mb * seq * args.steps
     tps = tokens / dt_max
-    flops_tok = cfg.flops_per_token(seq)
+    flops_tok = cfg.flops_per_token(seq, doc_info["visible_fraction"] if doc_info else None)
     mfu = flops_tok * tps / (MI355X_BF16_DENSE_PEAK * world)
     peak_mem = torch.cuda.max_memory_allocated(dev) if dev.type == "cuda" else 0
     final_loss = float(torch.stack(losses).float().mean().item()) if losses else float("nan")
@@ -219,7 +270,10 @@ def run_ddp_bench(args) -> dict:
         "vs_baseline": None,
         "dtype": "bf16",
         "linear_dtype": cfg.linear_dtype,
-        "data": "synthetic (uniform random token ids), random-init weights",
+        "data": "synthetic (uniform random token ids), random-init weights"
+                + (f", rows packed with documents of mean length {doc_len} (attention masked at "
+                   f"their boundaries)" if doc_info else ""),
+        "doc_mask": doc_info,
         "config": {"model": model_name, "global_batch": world * mb, "seq_len": seq,
                    "parallelism": f"dp{world}" + ("+zero1" if ddp.sharded else "")},
         "tokens_per_s_per_gpu": round(tps / world, 1),
@@ -259,6 +313,10 @@ def main(argv=None) -> int:
     p.add_argument("--linear-dtype", choices=["bf16", "mxfp8"], default=None,
                    help="products of wqkv / wo / w13 / w2: bf16 kernels (default) or the MXFP8 "
                         "GEMM; unset, the environment variable MXK_LINEAR_DTYPE decides")
+    p.add_argument("--doc-len", type=int, default=None, metavar="MEAN",
+                   help="pack each synthetic row with documents of this mean length and mask "
+                        "attention at their boundaries; unset, the environment variable "
+                        "MXK_DOC_LEN decides (default 0: off)")
     a = p.parse_args(argv)
     out = run_ddp_bench(a)
     if mxdist.world_info()[1] == 0:

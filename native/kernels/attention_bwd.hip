@@ -68,15 +68,22 @@ mxk_attn_bwd_delta_kernel(const uint16_t* __restrict__ o, const uint16_t* __rest
 // ROWC (with FOLD; backward variant 6): instead of delta, write the row
 // pair {-lse/scale, -delta} that the 256-key dK/dV kernel
 // (attention_bwd256.hip) loads as the initial S' / dP' accumulators.
+// DOC (mxk_attn_bwd_doc; with CAUSAL, DMA, PIPE and not UNROLL): causal
+// within a document, the forward's DOC form - the walk starts at the tile of
+// doc_start[q0], a wave skips the tiles before its first row's document, and
+// the tiles that begin before its last row's document zero P where
+// key < doc_start[row].
 template <bool CAUSAL, bool DMA = false, bool PIPE = false, bool UNROLL = false, bool FOLD = false,
-          bool ROWC = false>
+          bool ROWC = false, bool DOC = false>
 __global__ void __launch_bounds__(NT, 2)
 mxk_attn_bwd_dq_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
                        const uint16_t* __restrict__ v, const uint16_t* __restrict__ dout,
                        const float* __restrict__ lse, const float* __restrict__ delta,
                        uint16_t* __restrict__ dq, int S, int Hq, int Hkv, long q_tok, long k_tok,
                        long v_tok, float scale, const uint16_t* __restrict__ o = nullptr,
-                       float* __restrict__ delta_w = nullptr) {
+                       float* __restrict__ delta_w = nullptr,
+                       const int* __restrict__ doc_start = nullptr) {
+  static_assert(!DOC || (CAUSAL && DMA && PIPE && !UNROLL), "the DOC form extends the FOLD instance");
   __shared__ __attribute__((aligned(16))) char smem[2][2 * TILE_BYTES];   // [buf][K | V]
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -132,6 +139,16 @@ mxk_attn_bwd_dq_kernel(const uint16_t* __restrict__ q, const uint16_t* __restric
 
   const int kv_end = CAUSAL ? min(S, q0 + BQ) : S;
   const int nkv = kv_end / BKV;
+  // DOC: the block's first tile and the wave's bounds through uniform
+  // addresses (scalar loads), the lane's own row with its other row constants
+  int j_lo = 0, ds_w0 = 0, ds_w1 = 0, ds_row = 0;
+  if constexpr (DOC) {
+    const int* ds_b = doc_start + static_cast<long>(b) * S;
+    j_lo = attn_doc_first_tile(ds_b[q0], q0, BKV, 1);
+    ds_w0 = ds_b[qw0];
+    ds_w1 = ds_b[qw0 + 31];
+    ds_row = ds_b[myq];
+  }
   const int ld_row = tid >> 4, ld_ch = tid & 15;
   bf16x8_t kst[4], vst[4];
   auto load_tile = [&](int j) {
@@ -178,13 +195,14 @@ mxk_attn_bwd_dq_kernel(const uint16_t* __restrict__ q, const uint16_t* __restric
     }
   };
   if constexpr (DMA) {
-    issue(0, 0);
+    issue(j_lo, j_lo & 1);
     // consume the per-query loads here, so the compiler's vmcnt waits for
     // them sit before the loop and not inside it (where they would also wait
     // for the next tile's untracked DMA)
 #pragma unroll
     for (int s = 0; s < 8; ++s) asm volatile("" ::"v"(qf[s]), "v"(dof[s]));
     asm volatile("" ::"v"(lse2), "v"(dlt));
+    if constexpr (DOC) asm volatile("" ::"v"(ds_row));
     vm_wait0();
   } else {
     load_tile(0);
@@ -201,7 +219,7 @@ mxk_attn_bwd_dq_kernel(const uint16_t* __restrict__ q, const uint16_t* __restric
   const int tr_byte = 8 * (i16 & 1);
 
   if constexpr (!UNROLL) {
-  for (int j = 0; j < nkv; ++j) {
+  for (int j = j_lo; j < nkv; ++j) {
     const int buf = j & 1;
     // DMA: buffer buf^1 was last read in iteration j-1 (barrier-certified)
     if (j + 1 < nkv) {
@@ -209,7 +227,9 @@ mxk_attn_bwd_dq_kernel(const uint16_t* __restrict__ q, const uint16_t* __restric
       else load_tile(j + 1);
     }
     const int kv0 = j * BKV;
-    if (!CAUSAL || kv0 <= qw0 + 31) {
+    bool active = !CAUSAL || kv0 <= qw0 + 31;
+    if constexpr (DOC) active = active && attn_doc_tile_active(kv0, BKV, ds_w0);
+    if (active) {
       const char* kt = smem[buf];
       const char* vt = smem[buf] + TILE_BYTES;
       const bool diag = CAUSAL && kv0 + BKV - 1 > qw0;
@@ -268,6 +288,13 @@ mxk_attn_bwd_dq_kernel(const uint16_t* __restrict__ q, const uint16_t* __restric
 #pragma unroll
             for (int r = 0; r < 16; ++r)
               if (kv0 + 32 * kh + crow(r, h) > myq) s0[r] = 0.f;
+          }
+          if constexpr (DOC) {
+            if (attn_doc_tile_masked(kv0, ds_w1)) {   // wave-uniform
+#pragma unroll
+              for (int r = 0; r < 16; ++r)
+                if (kv0 + 32 * kh + crow(r, h) < ds_row) s0[r] = 0.f;
+            }
           }
 #pragma unroll
           for (int r = 0; r < 16; r += 2) {
@@ -720,7 +747,13 @@ constexpr int NT16 = 512;
 // ~1.1 GB more HBM traffic per Llama-3-8B layer at B = 8).
 // DMA: Q / dO slices by LDS-DMA (wave w moves the 1-KiB pieces 2w, 2w + 1 of
 // each), as in the dQ kernel; the lse / delta rows stay register-staged.
-template <bool CAUSAL, bool GQA = false, bool DMA = false, bool PIPE = false>
+// DOC (mxk_attn_bwd_doc; with CAUSAL, GQA, DMA and PIPE): causal within a
+// document, by the key's side of the rule - row i sees key j <= i iff
+// i < doc_end[j].  The walk ends at the slice of doc_end[k0 + 127] instead of
+// at S, a wave skips the slices that begin at or after its last key's
+// doc_end, and the slices that reach past its first key's doc_end zero P
+// where row >= doc_end[key].
+template <bool CAUSAL, bool GQA = false, bool DMA = false, bool PIPE = false, bool DOC = false>
 __global__ void __launch_bounds__(NT16, 1)
 mxk_attn_bwd_dkdv16_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
                            const uint16_t* __restrict__ v, const uint16_t* __restrict__ dout,
@@ -728,7 +761,9 @@ mxk_attn_bwd_dkdv16_kernel(const uint16_t* __restrict__ q, const uint16_t* __res
                            float* __restrict__ dk_p, float* __restrict__ dv_p, int S, int Hq,
                            int Hkv, long q_tok, long k_tok, long v_tok, float scale,
                            uint16_t* __restrict__ dk = nullptr, uint16_t* __restrict__ dv = nullptr,
-                           long dk_tok = 0, long dv_tok = 0) {
+                           long dk_tok = 0, long dv_tok = 0,
+                           const int* __restrict__ doc_end = nullptr) {
+  static_assert(!DOC || (CAUSAL && GQA && DMA && PIPE), "the DOC form extends the GQA DMA PIPE instance");
   __shared__ __attribute__((aligned(16))) char smem[2][2 * BQB * 256];   // [buf][Q | dO]
   __shared__ __attribute__((aligned(16))) float srow[2][2][BQB];       // [buf][-lse/scale | -delta]
   const int tid = threadIdx.x;
@@ -761,12 +796,23 @@ mxk_attn_bwd_dkdv16_kernel(const uint16_t* __restrict__ q, const uint16_t* __res
     kf[s] = *reinterpret_cast<const bf16x8_t*>(kb_ptr + static_cast<long>(mykey) * k_tok + 32 * s + 8 * G);
     vf[s] = *reinterpret_cast<const bf16x8_t*>(vb_ptr + static_cast<long>(mykey) * v_tok + 32 * s + 8 * G);
   }
+  // DOC: the block's last slice and the wave's bounds through uniform
+  // addresses (scalar loads), the lane's own key next to its K / V fragments
+  int de_blk = S, de_w0 = S, de_w1 = S, de_key = S;
+  if constexpr (DOC) {
+    const int* de_b = doc_end + static_cast<long>(b) * S;
+    de_blk = de_b[k0 + BQ - 1];
+    de_w0 = de_b[kw0];
+    de_w1 = de_b[kw0 + 15];
+    de_key = de_b[mykey];
+  }
   if constexpr (DMA) {
     // wait for the K / V fragments here, before the loops: a compiler wait
     // at their first use inside the slice loop would also wait for the
     // untracked DMA of the next slice
 #pragma unroll
     for (int s = 0; s < 4; ++s) asm volatile("" ::"v"(kf[s]), "v"(vf[s]));
+    if constexpr (DOC) asm volatile("" ::"v"(de_key));
   }
   const float c = scale * 1.4426950408889634f;
   const float inv_c = 1.f / c;
@@ -782,7 +828,7 @@ mxk_attn_bwd_dkdv16_kernel(const uint16_t* __restrict__ q, const uint16_t* __res
   const int tr_chb = (c16 & 3) >> 1;
   const int tr_byte = 8 * (c16 & 1);
   const int q_begin = CAUSAL ? k0 : 0;
-  const int nsl = (S - q_begin) / BQB;
+  const int nsl = DOC ? attn_doc_slices(de_blk, k0, S, BQB) : (S - q_begin) / BQB;
   // Work items i = (query slice t, head gq of the group), head-outer, slices
   // ascending from the diagonal; pipelined across head boundaries.  (A
   // slice-outer walk from the last slice down, heads inner, which keeps the
@@ -891,7 +937,9 @@ mxk_attn_bwd_dkdv16_kernel(const uint16_t* __restrict__ q, const uint16_t* __res
     int t, gq_unused;
     item(i, &t, &gq_unused);
     const int qs0 = q_begin + t * BQB;
-    if (!CAUSAL || qs0 + BQB - 1 >= kw0) {
+    bool active = !CAUSAL || qs0 + BQB - 1 >= kw0;
+    if constexpr (DOC) active = active && attn_doc_slice_active(qs0, de_w1);
+    if (active) {
       const char* qt = smem[buf];
       const char* dt = smem[buf] + BQB * 256;
       const bool diag = CAUSAL && qs0 < kw0 + 15;
@@ -966,6 +1014,15 @@ mxk_attn_bwd_dkdv16_kernel(const uint16_t* __restrict__ q, const uint16_t* __res
 #pragma unroll
               for (int r = 0; r < 4; ++r)
                 if (mykey > qs0 + 32 * ks + 16 * h + 4 * G + r) st[h][r] = 0.f;
+          }
+          if constexpr (DOC) {
+            if (attn_doc_slice_masked(qs0, BQB, de_w0)) {   // wave-uniform
+#pragma unroll
+              for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                  if (qs0 + 32 * ks + 16 * h + 4 * G + r >= de_key) st[h][r] = 0.f;
+            }
           }
 #pragma unroll
           for (int h = 0; h < 2; ++h)
@@ -1244,5 +1301,41 @@ MXK_API int mxk_attn_bwd_variant(const void* q, const void* k, const void* v, co
   const long n_out = static_cast<long>(B) * S * Hkv * D;
   hipLaunchKernelGGL(mxk_attn_bwd_gqa_reduce_kernel, dim3((n_out / 4 + 255) / 256), dim3(256), 0,
                      stream, a.dk_p, a.dv_p, a.dk, a.dv, n_out, Hq, Hkv, dk_tok, dv_tok);
+  MXK_RETURN_LAUNCH_STATUS();
+}
+
+MXK_API long mxk_attn_bwd_doc_workspace(int B, int S, int Hq) {
+  return attn_bwd_workspace(B, S, Hq, 5);   // delta
+}
+
+// Backward variant 5 with a per-document causal mask (attention_plan.h):
+// the FOLD dQ kernel's DOC form, writing delta, then the GQA DMA PIPE dK / dV
+// kernel's.  doc_start / doc_end int32 [B, S]; workspace:
+// mxk_attn_bwd_doc_workspace bytes.  hipErrorInvalidValue, with nothing
+// launched, for a layout attn_doc_ok does not take or a null / misaligned
+// pointer.
+MXK_API int mxk_attn_bwd_doc(const void* q, const void* k, const void* v, const void* o,
+                             const void* dout, const float* lse, void* dq, void* dk, void* dv,
+                             void* workspace, const int* doc_start, const int* doc_end, int B,
+                             int S, int Hq, int Hkv, int head_dim, long q_tok, long k_tok,
+                             long v_tok, long dk_tok, long dv_tok, float scale,
+                             hipStream_t stream) {
+  const AttnLayout L{B, S, Hq, Hkv, q_tok, k_tok, v_tok, static_cast<long>(Hq) * D, dk_tok, dv_tok, 1};
+  if (head_dim != D || !attn_doc_ok(L) || !q || !k || !v || !o || !dout || !lse || !dq || !dk ||
+      !dv || !workspace || !doc_start || !doc_end ||
+      !attn_aligned(16, q, k, v, o, dout, dq, workspace) || !attn_aligned(8, dk, dv) ||
+      !attn_aligned(4, lse, doc_start, doc_end))
+    return static_cast<int>(hipErrorInvalidValue);
+  float* delta = static_cast<float*>(workspace);
+  hipLaunchKernelGGL((mxk_attn_bwd_dq_kernel<true, true, true, false, true, false, true>),
+                     dim3(B * Hq * (S / BQ)), dim3(NT), 0, stream, bf(q), bf(k), bf(v), bf(dout),
+                     lse, nullptr, bf(dq), S, Hq, Hkv, q_tok, k_tok, v_tok, scale, bf(o), delta,
+                     doc_start);
+  const int st = static_cast<int>(hipGetLastError());
+  if (st) return st;
+  hipLaunchKernelGGL((mxk_attn_bwd_dkdv16_kernel<true, true, true, true, true>),
+                     dim3(B * Hkv * (S / BQ)), dim3(NT16), 0, stream, bf(q), bf(k), bf(v),
+                     bf(dout), lse, delta, nullptr, nullptr, S, Hq, Hkv, q_tok, k_tok, v_tok, scale,
+                     bf(dk), bf(dv), dk_tok, dv_tok, doc_end);
   MXK_RETURN_LAUNCH_STATUS();
 }

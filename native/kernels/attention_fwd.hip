@@ -208,12 +208,18 @@ mxk_attn_fwd_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__
 //     v_pk_add_f32), halving the softmax's full-rate VALU work.
 // Requires S * token_stride * 2 < 2^32 for K and V (buffer offsets).
 
-template <bool CAUSAL, bool UNROLL, bool PIPE = false>
+// DOC (mxk_attn_fwd_doc; with CAUSAL): causal within a document.  The walk
+// starts at the tile of doc_start[q0] (rounded down to an even tile under
+// UNROLL, so the LDS buffers stay compile-time), a wave skips the tiles that
+// end before its first row's document, and the tiles that begin before its
+// last row's document mask key < doc_start[row] per score.
+template <bool CAUSAL, bool UNROLL, bool PIPE = false, bool DOC = false>
 __global__ void __launch_bounds__(NT, 2)
 mxk_attn_fwd_dma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
                         const uint16_t* __restrict__ v, uint16_t* __restrict__ o,
                         float* __restrict__ lse, int S, int Hq, int Hkv, long q_tok, long k_tok,
-                        long v_tok, float scale) {
+                        long v_tok, float scale, const int* __restrict__ doc_start = nullptr) {
+  static_assert(!DOC || CAUSAL, "a document table masks causal attention only");
   __shared__ __attribute__((aligned(16))) char smem[2][2 * TILE_BYTES];   // [buf][K | V]
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -241,6 +247,16 @@ mxk_attn_fwd_dma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restri
 
   const int kv_end = CAUSAL ? min(S, q0 + BQ) : S;
   const int nkv = kv_end / BKV;
+  // DOC: the block's first tile and the wave's bounds through uniform
+  // addresses (scalar loads), the lane's own row next to its Q fragments
+  int j_lo = 0, ds_w0 = 0, ds_w1 = 0, ds_row = 0;
+  if constexpr (DOC) {
+    const int* ds_b = doc_start + static_cast<long>(b) * S;
+    j_lo = attn_doc_first_tile(ds_b[q0], q0, BKV, UNROLL ? 2 : 1);
+    ds_w0 = ds_b[qw0];
+    ds_w1 = ds_b[qw0 + 31];
+    ds_row = ds_b[myq];
+  }
 
   // DMA: wave w moves the 1-KiB pieces g = 4w + p (rows 4g .. 4g+3) of K and
   // V; lane i lands at row 4g + (i >> 4), slot i & 15, so it fetches chunk
@@ -269,7 +285,7 @@ mxk_attn_fwd_dma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restri
       mxk::dma16m(rv, d + TILE_BYTES, vvo[p], j * v_step);
     }
   };
-  issue(0, 0);
+  issue(j_lo, j_lo & 1);
 
   // loop-invariant LDS read offsets: K rows r32 (+32 rows = +8 KiB), chunk
   // 2s + h; V transposed reads at keys tr_key (+8), chunk 4db + tr_ch, with
@@ -290,7 +306,13 @@ mxk_attn_fwd_dma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restri
 
   const float c = scale * 1.4426950408889634f;   // scores -> log2 domain
   const f32x2_t cc = {c, c};
-  float m = -INFINITY, l = 0.f;
+  // DOC: a row whose document starts after an active tile has every score of
+  // that tile at -inf.  With m = -inf the shift would be -inf + inf = NaN;
+  // from a finite floor no score reaches, m_new stays the floor, the shift
+  // m c is finite, P = exp2(-inf) = 0 and alpha = 1: the lane's m, l and acc
+  // stay as they were.  The first visible score then rescales by
+  // exp2(-huge) = 0, as it does from -inf.
+  float m = DOC ? -1.7e38f / fmaxf(1.f, c) : -INFINITY, l = 0.f;
   f32x16_t acc[4];
 #pragma unroll
   for (int db = 0; db < 4; ++db)
@@ -302,7 +324,8 @@ mxk_attn_fwd_dma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restri
   // would also wait for the next tile's (untracked) DMA.
 #pragma unroll
   for (int s = 0; s < 8; ++s) asm volatile("" ::"v"(qf[s]));
-  vm_wait0();   // tile 0
+  if constexpr (DOC) asm volatile("" ::"v"(ds_row));
+  vm_wait0();   // tile 0 (DOC: tile j_lo)
   __syncthreads();
 
   // the loop body; UNROLL makes the LDS buffer a compile-time constant (read
@@ -311,7 +334,8 @@ mxk_attn_fwd_dma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restri
     // buffer buf^1 was last read in iteration j-1 (barrier-certified)
     if (j + 1 < nkv) issue(j + 1, buf ^ 1);
     const int kv0 = j * BKV;
-    const bool active = !CAUSAL || kv0 <= qw0 + 31;
+    bool active = !CAUSAL || kv0 <= qw0 + 31;
+    if constexpr (DOC) active = active && attn_doc_tile_active(kv0, BKV, ds_w0);
     if (active) {
       const char* kt = smem[buf];
       const char* vt = smem[buf] + TILE_BYTES;
@@ -367,6 +391,16 @@ mxk_attn_fwd_dma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restri
           const int key = kv0 + crow(r, h);
           if (key > myq) s0[r] = -INFINITY;
           if (key + 32 > myq) s1[r] = -INFINITY;
+        }
+      }
+      if constexpr (DOC) {
+        if (attn_doc_tile_masked(kv0, ds_w1)) {   // wave-uniform
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int key = kv0 + crow(r, h);
+            if (key < ds_row) s0[r] = -INFINITY;
+            if (key + 32 < ds_row) s1[r] = -INFINITY;
+          }
         }
       }
       float mx = s0[0];
@@ -476,12 +510,12 @@ mxk_attn_fwd_dma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restri
     __syncthreads();
   };
   if constexpr (UNROLL) {
-    for (int j = 0; j < nkv; j += 2) {
+    for (int j = j_lo; j < nkv; j += 2) {   // j_lo is even
       step(j, 0);
       if (j + 1 < nkv) step(j + 1, 1);
     }
   } else {
-    for (int j = 0; j < nkv; ++j) step(j, j & 1);
+    for (int j = j_lo; j < nkv; ++j) step(j, j & 1);
   }
 
   const float lt = half_sum(l);
@@ -582,4 +616,21 @@ MXK_API int mxk_attn_fwd_variant_built(int v) {
 #else
   return v >= 0 && v <= 4;
 #endif
+}
+
+// Forward variant 4 with a per-document causal mask (attention_plan.h):
+// doc_start int32 [B, S].  hipErrorInvalidValue, with nothing launched, for a
+// layout attn_doc_ok does not take or a null / misaligned pointer.
+MXK_API int mxk_attn_fwd_doc(const void* q, const void* k, const void* v, void* o, float* lse,
+                             const int* doc_start, int B, int S, int Hq, int Hkv, int head_dim,
+                             long q_tok, long k_tok, long v_tok, float scale, hipStream_t stream) {
+  const AttnLayout L{B, S, Hq, Hkv, q_tok, k_tok, v_tok, static_cast<long>(Hq) * D,
+                     static_cast<long>(Hkv) * D, static_cast<long>(Hkv) * D, 1};
+  if (head_dim != D || !attn_doc_ok(L) || !q || !k || !v || !o || !lse || !doc_start ||
+      !attn_aligned(16, q, k, v, o) || !attn_aligned(4, lse, doc_start))
+    return static_cast<int>(hipErrorInvalidValue);
+  hipLaunchKernelGGL((mxk_attn_fwd_dma_kernel<true, true, true, true>), dim3(B * Hq * (S / BQ)),
+                     dim3(NT), 0, stream, bf(q), bf(k), bf(v), bf(o), lse, S, Hq, Hkv, q_tok, k_tok,
+                     v_tok, scale, doc_start);
+  MXK_RETURN_LAUNCH_STATUS();
 }

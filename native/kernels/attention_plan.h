@@ -1,6 +1,7 @@
-// Which flash-attention kernel takes which layout, and the plan of the
-// backward: plain host C++17, no device code and no HIP call, so the kernel
-// library and a stand-alone host program (native/kernels/tests/) share it.
+// Which flash-attention kernel takes which layout, the plan of the backward
+// and the tile bounds of the document mask: plain C++17 with no HIP call (the
+// bounds constexpr, so device code may call them), so the kernel library and
+// the stand-alone host programs (native/kernels/tests/) share it.
 // Every launcher and dispatcher of attention_*.hip asks these predicates;
 // pointer alignment, which a layout does not carry, stays at the entry points.
 #pragma once
@@ -62,6 +63,47 @@ inline bool attn_dkdv256_ok(const AttnLayout& L) {
   return attn_shape_ok(L, KBLK) && L.dk_tok % 4 == 0 && L.dv_tok % 4 == 0 &&
          attn_fits(L, L.q_tok) && attn_fits(L, L.k_tok) &&
          attn_fits(L, static_cast<long>(L.Hq) * D);
+}
+
+// ---------------------------------------------------------------------------
+// Packed sequences: causal attention within a document.  doc_start[b][i] is
+// the first token of the document token i belongs to, doc_end[b][j] the
+// (exclusive) end of j's document; both int32 [B, S] and non-decreasing along
+// a row.  Query i sees key j iff doc_start[i] <= j <= i, which for j <= i is
+// the same as i < doc_end[j].  The DOC forms of forward variant 4 and backward
+// variant 5 (mxk_attn_fwd_doc / mxk_attn_bwd_doc) are the LDS-DMA kernels
+// only: there is no register-staged fallback.
+inline bool attn_doc_ok(const AttnLayout& L) {
+  return L.causal && attn_bwd_ok(L) && attn_kv_dma_ok(L) && attn_q_dma_ok(L);
+}
+// The tile / slice bounds those kernels derive from the tables, constexpr so
+// that the kernels and the host test share one definition.  Every result is
+// clamped into the causal range, whatever the table holds: a malformed table
+// gives wrong numbers, never an index outside the tensors.
+constexpr int attn_clampi(int x, int lo, int hi) { return x < lo ? lo : x > hi ? hi : x; }
+// forward / dQ: the first `tile`-key tile of the K / V walk of the query block
+// at row q0 (ds_q0 = doc_start[q0], the smallest of the block), a multiple of
+// `align` tiles (2 for a loop unrolled by two over static LDS buffers); the
+// walk ends at the diagonal tile (q0 + BQ) / tile - 1 as without a table
+constexpr int attn_doc_first_tile(int ds_q0, int q0, int tile, int align) {
+  return attn_clampi(ds_q0, 0, q0) / (tile * align) * align;
+}
+// a wave whose first row's document starts at ds_first has a visible key in
+// the tile at kv0 (the causal test is separate)
+constexpr bool attn_doc_tile_active(int kv0, int tile, int ds_first) { return kv0 + tile > ds_first; }
+// ... and needs the per-score mask key < doc_start[row] there (ds_last: of its last row)
+constexpr bool attn_doc_tile_masked(int kv0, int ds_last) { return kv0 < ds_last; }
+// dK / dV: `slice`-row query slices the key block at k0 walks from the
+// diagonal (de_last = doc_end[k0 + BQ - 1], the largest of the block)
+constexpr int attn_doc_slices(int de_last, int k0, int S, int slice) {
+  return (attn_clampi(de_last, k0 + BQ, S) - k0 + slice - 1) / slice;
+}
+// a wave whose last key's document ends at de_last has a visible query row in
+// the slice at qs0 (the causal test is separate)
+constexpr bool attn_doc_slice_active(int qs0, int de_last) { return qs0 < de_last; }
+// ... and needs the per-score mask row >= doc_end[key] there (de_first: of its first key)
+constexpr bool attn_doc_slice_masked(int qs0, int slice, int de_first) {
+  return qs0 + slice > de_first;
 }
 
 // ---------------------------------------------------------------------------
