@@ -12,6 +12,7 @@
 #   make test-native-tsan  libmxnode re-entrancy test under ThreadSanitizer
 #   make test-attention-plan  the attention backward plan's sweep (host, ASan+UBSan build)
 #   make test-attention-doc   the document-mask predicate and tile bounds (host, ASan+UBSan build)
+#   make test-mxfp4-format    the e2m1 conversion and block exponent over every bf16 (host, ASan+UBSan build)
 #
 # Everything lands inside the repo so `gpurun` snapshots carry it to the box.
 
@@ -31,7 +32,7 @@ LDLIBS_NODE := -ldl -lpthread
 KERNEL_SRCS := native/kernels/gemm_bf16.hip native/kernels/vector_add.hip \
                native/kernels/fused_ops.hip native/kernels/optim.hip native/kernels/attention_fwd.hip native/kernels/attention_bwd.hip native/kernels/attention_bwd256.hip native/kernels/attention_fwd256.hip native/kernels/attention_dq256.hip \
                native/kernels/gemm_bf16_layouts.hip native/kernels/xent.hip native/kernels/contention.hip \
-               native/kernels/gemm_mxfp8.hip
+               native/kernels/gemm_mxfp8.hip native/kernels/gemm_mxfp4.hip
 KERNEL_OBJS := $(patsubst native/kernels/%.hip,$(BUILD)/kernels/%.o,$(KERNEL_SRCS))
 EXP_SRCS    := $(KERNEL_SRCS) $(wildcard native/kernels/experiments/*.hip)
 EXP_OBJS    := $(patsubst native/kernels/%.hip,$(BUILD)/exp/%.o,$(EXP_SRCS))
@@ -41,7 +42,7 @@ NODE_SRCS := $(wildcard native/libmxnode/*.cc)
 NODE_OBJS := $(patsubst native/libmxnode/%.cc,$(BUILD)/node/%.o,$(NODE_SRCS))
 NODE_HDRS := $(wildcard native/libmxnode/*.h)
 
-.PHONY: all kernels gemm-exp node tools clean test-native test-native-tsan test-attention-plan test-attention-doc fake-amdsmi
+.PHONY: all kernels gemm-exp node tools clean test-native test-native-tsan test-attention-plan test-attention-doc test-mxfp4-format fake-amdsmi
 all: kernels node tools fake-amdsmi
 
 kernels: $(OUT_LIB)/libmxkernels.so
@@ -104,7 +105,7 @@ $(OUT_BIN)/mx-vector-add: $(BUILD)/tools/vector_add_main.o $(BUILD)/kernels/vect
 	$(HIPCC) --offload-arch=$(ARCH) -o $@ $^
 
 $(OUT_BIN)/mx-gemm-bench: $(BUILD)/tools/gemm_bench_main.o $(BUILD)/kernels/gemm_bf16.o $(BUILD)/kernels/gemm_bf16_layouts.o \
-                         $(BUILD)/kernels/gemm_mxfp8.o
+                         $(BUILD)/kernels/gemm_mxfp8.o $(BUILD)/kernels/gemm_mxfp4.o
 	@mkdir -p $(OUT_BIN)
 	$(HIPCC) --offload-arch=$(ARCH) -o $@ $^ -L$(ROCM)/lib -lrocblas -lrocprofiler-sdk-roctx -Wl,-rpath,$(ROCM)/lib
 
@@ -148,6 +149,14 @@ test-attention-doc: $(BUILD)/asan/attention_doc_sweep
 	$<
 
 $(BUILD)/asan/attention_doc_sweep: native/kernels/tests/attention_doc_sweep.cc native/kernels/attention_plan.h
+	@mkdir -p $(dir $@)
+	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -Wshadow -fsanitize=address,undefined -fno-sanitize-recover=all \
+	    -fno-omit-frame-pointer -Inative/kernels -o $@ $<
+
+test-mxfp4-format: $(BUILD)/asan/mxfp4_format_sweep
+	$<
+
+$(BUILD)/asan/mxfp4_format_sweep: native/kernels/tests/mxfp4_format_sweep.cc native/kernels/mxfp4_format.h
 	@mkdir -p $(dir $@)
 	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -Wshadow -fsanitize=address,undefined -fno-sanitize-recover=all \
 	    -fno-omit-frame-pointer -Inative/kernels -o $@ $<

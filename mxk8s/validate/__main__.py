@@ -11,7 +11,9 @@ lines; the process exits non-zero if any test fails.
   gemm       CDNA4 bf16 MFMA GEMM TFLOPS vs rocBLAS (bin/mx-gemm-bench) config 3
              --gemm-dtypes bf16,mxfp8 adds the MXFP8 pass: block-scaled e4m3
              operands quantised on the GPU, the scaled-MFMA GEMM checked against
-             the product of the dequantised operands (mx-gemm-bench --dtype mxfp8)
+             the product of the dequantised operands (mx-gemm-bench --dtype mxfp8);
+             mxfp4 does the same for block-scaled e2m1 (--dtype mxfp4), the
+             part's fastest matrix path
   rccl       RCCL all-reduce sweep over xGMI (bin/mx-allreduce-perf)  config 4
   ddp        Llama-3-8B DDP synthetic training step (bench.py --mode ddp) config 5
 
@@ -81,11 +83,11 @@ def test_vectoradd() -> bool:
     return rc == 0 and bool(rs) and all(r.get("pass") for r in rs)
 
 
-GEMM_DTYPES = ("bf16", "mxfp8")
+GEMM_DTYPES = ("bf16", "mxfp8", "mxfp4")
 
 
 def parse_gemm_dtypes(arg: str) -> list[str]:
-    """``--gemm-dtypes``: a comma list of bf16 / mxfp8 without repeats."""
+    """``--gemm-dtypes``: a comma list of bf16 / mxfp8 / mxfp4 without repeats."""
     out = [d for d in arg.split(",") if d]
     bad = [d for d in out if d not in GEMM_DTYPES]
     if bad or not out or len(set(out)) != len(out):
@@ -193,7 +195,7 @@ def main(argv=None) -> int:
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--gemm-sizes", default="4096,8192,16384")
     p.add_argument("--gemm-dtypes", default="bf16",
-                   help="comma list of bf16,mxfp8: mx-gemm-bench runs once per dtype")
+                   help="comma list of bf16,mxfp8,mxfp4: mx-gemm-bench runs once per dtype")
     p.add_argument("--rccl-min-bytes", type=int, default=8)
     p.add_argument("--rccl-max-bytes", type=int, default=1 << 33)
     p.add_argument("--rccl-scaling", default="")

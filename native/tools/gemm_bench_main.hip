@@ -8,7 +8,7 @@
 // Protocol: >= warmup_ms of back-to-back launches, then the median of `iters`
 // hipEvent-timed launches (BASELINE.md "Measurement protocol").
 //   mx-gemm-bench [--sizes 4096,8192,16384] [--iters 50] [--warmup-ms 2000]
-//                 [--devices all|0,1] [--no-ref] [--dtype bf16|mxfp8]
+//                 [--devices all|0,1] [--no-ref] [--dtype bf16|mxfp8|mxfp4]
 // --dtype mxfp8 runs the block-scaled e4m3 path instead
 // (native/kernels/gemm_mxfp8.hip): the same bf16 operands are quantised on the
 // GPU (32-element blocks, E8M0 scales), the scaled-MFMA kernel is checked on
@@ -16,6 +16,9 @@
 // operands (fp8's own error against the bf16 product is ~7 %, so that product
 // is no reference), and timed by the same protocol.  rel_err_vs_rocblas is
 // null there: the binary has no library reference for the format.
+// --dtype mxfp4 does the same for block-scaled e2m1, two codes per byte
+// (native/kernels/gemm_mxfp4.hip); its own error against the bf16 product is
+// ~21 % on this data.
 #include <hip/hip_runtime.h>
 #include <rocblas/rocblas.h>
 #include <rocprofiler-sdk-roctx/roctx.h>
@@ -40,6 +43,12 @@ extern "C" int mxk_gemm_mxfp8_tn(const void* Aq, const void* As, const void* Bq,
                                  void* C, int M, int N, int K, int lda, int ldsa, int ldb, int ldsb,
                                  int ldc, hipStream_t stream);
 extern "C" int mxk_quantize_mxfp8(const void* x, void* q, void* s, long R, int K, long ldx, long ldq,
+                                  long lds, hipStream_t stream);
+
+extern "C" int mxk_gemm_mxfp4_tn(const void* Aq, const void* As, const void* Bq, const void* Bs,
+                                 void* C, int M, int N, int K, int lda, int ldsa, int ldb, int ldsb,
+                                 int ldc, hipStream_t stream);
+extern "C" int mxk_quantize_mxfp4(const void* x, void* q, void* s, long R, int K, long ldx, long ldq,
                                   long lds, hipStream_t stream);
 
 namespace {
@@ -127,8 +136,39 @@ __global__ void spot_check_mxfp8(const uint8_t* Aq, const uint8_t* As, const uin
   atomicMax(max_ref, __float_as_uint(fabsf(acc)));
 }
 
+// e2m1 nibble (magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6; bit 3 the sign) -> fp32
+__device__ float e2m1_nibble_to_f32(uint8_t c) {
+  const int e = (c >> 1) & 3, m = c & 1;
+  const float mag = e ? ldexpf(1.f + 0.5f * m, e - 1) : 0.5f * m;
+  return c & 8 ? -mag : mag;
+}
+
+// spot_check for the MXFP4 path: rows of n / 2 bytes, element k in the low
+// (even k) or high (odd k) nibble of byte k / 2.
+__global__ void spot_check_mxfp4(const uint8_t* Aq, const uint8_t* As, const uint8_t* Bq,
+                                 const uint8_t* Bs, const uint16_t* C, int n, int r0, int c0,
+                                 unsigned* max_err, unsigned* max_ref) {
+  const int r = r0 + blockIdx.x, c = c0 + threadIdx.x;
+  const uint8_t* a = Aq + size_t(r) * (n / 2);
+  const uint8_t* b = Bq + size_t(c) * (n / 2);
+  const uint8_t* sa = As + size_t(r) * (n / 32);
+  const uint8_t* sb = Bs + size_t(c) * (n / 32);
+  float acc = 0.f;
+  for (int k = 0; k < n; ++k) {
+    const int sh = 4 * (k & 1);
+    acc = fmaf(e2m1_nibble_to_f32((a[k >> 1] >> sh) & 15) * e8m0_to_f32(sa[k >> 5]),
+               e2m1_nibble_to_f32((b[k >> 1] >> sh) & 15) * e8m0_to_f32(sb[k >> 5]), acc);
+  }
+  const float got = __uint_as_float(uint32_t(C[size_t(r) * n + c]) << 16);
+  const float err = fabsf(got - acc);
+  atomicMax(max_err, __float_as_uint(err == err ? err : INFINITY));   // NaN -> inf
+  atomicMax(max_ref, __float_as_uint(fabsf(acc)));
+}
+
+enum class Dtype { bf16, mxfp8, mxfp4 };
+
 struct Opts {
-  bool mxfp8 = false;
+  Dtype dtype = Dtype::bf16;
   std::vector<int> sizes{4096, 8192, 16384};
   int iters = 50;
   int warmup_ms = 2000;
@@ -272,9 +312,15 @@ bool run_device(int dev, const Opts& o) {
   return all_ok;
 }
 
-// --dtype mxfp8: quantise, poison, launch, spot-check against the dequantised
-// operands, then the bf16 path's warm-up floor and median-of-iters timing.
-bool run_device_mxfp8(int dev, const Opts& o) {
+// --dtype mxfp8 / mxfp4: quantise, poison, launch, spot-check against the
+// dequantised operands, then the bf16 path's warm-up floor and median-of-iters
+// timing.  The two formats differ in the row bytes (n or n / 2) and the entry
+// points.
+bool run_device_mx(int dev, const Opts& o) {
+  const bool fp4 = o.dtype == Dtype::mxfp4;
+  const char* name = fp4 ? "mxfp4" : "mxfp8";
+  const auto quantize = fp4 ? mxk_quantize_mxfp4 : mxk_quantize_mxfp8;
+  const auto gemm = fp4 ? mxk_gemm_mxfp4_tn : mxk_gemm_mxfp8_tn;
   bool all_ok = true;
   if (hipSetDevice(dev) != hipSuccess) return false;
   hipStream_t st;
@@ -282,14 +328,15 @@ bool run_device_mxfp8(int dev, const Opts& o) {
   for (int n : o.sizes) {
     const size_t elems = size_t(n) * n;
     const int nb = n / 32;
+    const int ldq = fp4 ? n / 2 : n;   // bytes of a quantised row
     uint16_t *A = nullptr, *B = nullptr, *C = nullptr;
     uint8_t *Aq = nullptr, *Bq = nullptr, *As = nullptr, *Bs = nullptr;
     if (hipMalloc(&A, elems * 2) || hipMalloc(&B, elems * 2) || hipMalloc(&C, elems * 2) ||
-        hipMalloc(&Aq, elems) || hipMalloc(&Bq, elems) || hipMalloc(&As, size_t(n) * nb) ||
+        hipMalloc(&Aq, size_t(n) * ldq) || hipMalloc(&Bq, size_t(n) * ldq) || hipMalloc(&As, size_t(n) * nb) ||
         hipMalloc(&Bs, size_t(n) * nb)) {
       std::lock_guard<std::mutex> lk(g_print);
-      std::printf("RESULT {\"test\":\"gemm\",\"gpu\":%d,\"M\":%d,\"dtype\":\"mxfp8\",\"pass\":false,"
-                  "\"error\":\"alloc\"}\n", dev, n);
+      std::printf("RESULT {\"test\":\"gemm\",\"gpu\":%d,\"M\":%d,\"dtype\":\"%s\",\"pass\":false,"
+                  "\"error\":\"alloc\"}\n", dev, n, name);
       all_ok = false;
       for (void* p : {(void*)A, (void*)B, (void*)C, (void*)Aq, (void*)Bq, (void*)As, (void*)Bs})
         if (p) CK(hipFree(p));
@@ -302,11 +349,11 @@ bool run_device_mxfp8(int dev, const Opts& o) {
     CK(hipEventCreate(&e0));
     CK(hipEventCreate(&e1));
     // quantise both operands on the GPU (run once untimed, then timed)
-    int qst = mxk_quantize_mxfp8(A, Aq, As, n, n, n, n, nb, st);
-    if (!qst) qst = mxk_quantize_mxfp8(B, Bq, Bs, n, n, n, n, nb, st);
+    int qst = quantize(A, Aq, As, n, n, n, ldq, nb, st);
+    if (!qst) qst = quantize(B, Bq, Bs, n, n, n, ldq, nb, st);
     CK(hipEventRecord(e0, st));
-    if (!qst) qst = mxk_quantize_mxfp8(A, Aq, As, n, n, n, n, nb, st);
-    if (!qst) qst = mxk_quantize_mxfp8(B, Bq, Bs, n, n, n, n, nb, st);
+    if (!qst) qst = quantize(A, Aq, As, n, n, n, ldq, nb, st);
+    if (!qst) qst = quantize(B, Bq, Bs, n, n, n, ldq, nb, st);
     CK(hipEventRecord(e1, st));
     CK(hipEventSynchronize(e1));
     float quantize_ms = 0;
@@ -318,7 +365,7 @@ bool run_device_mxfp8(int dev, const Opts& o) {
     const char* skip = std::getenv("MXK_GEMM_BENCH_SKIP_KERNEL");   // fault-injection hook
     int launch_st = 0;
     if (!(skip && *skip == '1'))
-      launch_st = mxk_gemm_mxfp8_tn(Aq, As, Bq, Bs, C, n, n, n, n, nb, n, nb, n, st);
+      launch_st = gemm(Aq, As, Bq, Bs, C, n, n, n, ldq, nb, ldq, nb, n, st);
     const hipError_t le = hipGetLastError();
     if (err_msg.empty() && (launch_st != 0 || le != hipSuccess))
       err_msg = std::string("kernel launch failed: ") +
@@ -331,8 +378,8 @@ bool run_device_mxfp8(int dev, const Opts& o) {
     const uint32_t h32 = (0x9E3779B1u * uint32_t(n)) ^ (0x85EBCA6Bu * uint32_t(dev + 1));
     const int blocks = n / 256;
     const int r0 = int(h32 % uint32_t(blocks)) * 256, c0 = int((h32 >> 16) % uint32_t(blocks)) * 256;
-    hipLaunchKernelGGL(spot_check_mxfp8, dim3(256), dim3(256), 0, st, Aq, As, Bq, Bs, C, n, r0, c0,
-                       dmax, dmax + 1);
+    hipLaunchKernelGGL(fp4 ? spot_check_mxfp4 : spot_check_mxfp8, dim3(256), dim3(256), 0, st, Aq, As,
+                       Bq, Bs, C, n, r0, c0, dmax, dmax + 1);
     CK(hipGetLastError());
     CK(hipMemcpyAsync(hmax, dmax, 8, hipMemcpyDeviceToHost, st));
     CK(hipStreamSynchronize(st));
@@ -345,10 +392,10 @@ bool run_device_mxfp8(int dev, const Opts& o) {
     if (err_msg.empty() && !spot_ok)
       err_msg = max_ref > 0.f ? "fp32 spot check failed" : "fp32 spot check: reference block is zero";
     float spent = 0;
-    roctxRangePushA("gemm_mxfp8.warmup");
+    roctxRangePushA(fp4 ? "gemm_mxfp4.warmup" : "gemm_mxfp8.warmup");
     while (spent < o.warmup_ms) {
       CK(hipEventRecord(e0, st));
-      for (int i = 0; i < 10; ++i) mxk_gemm_mxfp8_tn(Aq, As, Bq, Bs, C, n, n, n, n, nb, n, nb, n, st);
+      for (int i = 0; i < 10; ++i) gemm(Aq, As, Bq, Bs, C, n, n, n, ldq, nb, ldq, nb, n, st);
       CK(hipEventRecord(e1, st));
       CK(hipEventSynchronize(e1));
       float ms;
@@ -357,10 +404,10 @@ bool run_device_mxfp8(int dev, const Opts& o) {
     }
     roctxRangePop();
     std::vector<float> t(o.iters);
-    roctxRangePushA("gemm_mxfp8.timed");
+    roctxRangePushA(fp4 ? "gemm_mxfp4.timed" : "gemm_mxfp8.timed");
     for (int i = 0; i < o.iters; ++i) {
       CK(hipEventRecord(e0, st));
-      mxk_gemm_mxfp8_tn(Aq, As, Bq, Bs, C, n, n, n, n, nb, n, nb, n, st);
+      gemm(Aq, As, Bq, Bs, C, n, n, n, ldq, nb, ldq, nb, n, st);
       CK(hipEventRecord(e1, st));
       CK(hipEventSynchronize(e1));
       CK(hipEventElapsedTime(&t[i], e0, e1));
@@ -373,11 +420,11 @@ bool run_device_mxfp8(int dev, const Opts& o) {
     all_ok &= pass;
     {
       std::lock_guard<std::mutex> lk(g_print);
-      std::printf("RESULT {\"test\":\"gemm\",\"gpu\":%d,\"M\":%d,\"N\":%d,\"K\":%d,\"dtype\":\"mxfp8\","
+      std::printf("RESULT {\"test\":\"gemm\",\"gpu\":%d,\"M\":%d,\"N\":%d,\"K\":%d,\"dtype\":\"%s\","
                   "\"median_ms\":%.4f,\"min_ms\":%.4f,\"tflops\":%.1f,\"rel_err_vs_rocblas\":null,"
                   "\"spot_block\":[%d,%d],\"max_abs_err\":%s,\"spot_tolerance\":%.4g,"
                   "\"quantize_ms\":%.4f,\"pass\":%s%s%s%s}\n",
-                  dev, n, n, n, med * 1e3, t[0], tflops, r0, c0, json_num(max_abs_err).c_str(),
+                  dev, n, n, n, name, med * 1e3, t[0], tflops, r0, c0, json_num(max_abs_err).c_str(),
                   spot_tol, quantize_ms,
                   pass ? "true" : "false", err_msg.empty() ? "" : ",\"error\":\"",
                   err_msg.c_str(), err_msg.empty() ? "" : "\"");
@@ -412,8 +459,9 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[i], "--no-ref")) o.ref = false;
     else if (!std::strcmp(argv[i], "--dtype") && i + 1 < argc) {
       const char* v = argv[++i];
-      if (!std::strcmp(v, "mxfp8")) o.mxfp8 = true;
-      else if (std::strcmp(v, "bf16")) { std::fprintf(stderr, "--dtype must be bf16 or mxfp8\n"); return 2; }
+      if (!std::strcmp(v, "mxfp8")) o.dtype = Dtype::mxfp8;
+      else if (!std::strcmp(v, "mxfp4")) o.dtype = Dtype::mxfp4;
+      else if (std::strcmp(v, "bf16")) { std::fprintf(stderr, "--dtype must be bf16, mxfp8 or mxfp4\n"); return 2; }
     } else if (!std::strcmp(argv[i], "--devices") && i + 1 < argc) {
       const char* v = argv[++i];
       if (std::strcmp(v, "all")) { o.devices = parse_list(v); all = false; }
@@ -430,7 +478,7 @@ int main(int argc, char** argv) {
   std::atomic<bool> ok{true};
   std::vector<std::thread> th;
   for (int d : o.devices)
-    th.emplace_back([&, d] { if (!(o.mxfp8 ? run_device_mxfp8(d, o) : run_device(d, o))) ok = false; });
+    th.emplace_back([&, d] { if (!(o.dtype == Dtype::bf16 ? run_device(d, o) : run_device_mx(d, o))) ok = false; });
   for (auto& t : th) t.join();
   return ok ? 0 : 1;
 }
