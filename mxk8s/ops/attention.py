@@ -9,7 +9,11 @@ returns o [B, S, Hq, 128] — the layout the output projection consumes, no
 transposes.  GQA: Hq % Hkv == 0.  The forward also produces the per-row
 log-sum-exp that the backward kernel uses to recompute P.
 
-``attention_ref`` is the fp32 PyTorch reference the tests compare against.
+``attention_ref`` is the fp32 PyTorch reference the tests compare against
+(float64 inputs stay float64).  The elementwise bounds of the kernels are
+checked against the fp64 reference in ``tests/attention_refs.py``
+(``attn_fwd_ref`` / ``attn_bwd_ref``, with the magnitude terms of the bounds
+and the adversarial input families) by ``tests/test_gpu_attention_numerics.py``.
 """
 from __future__ import annotations
 
@@ -168,16 +172,17 @@ def _check_doc(doc: DocMask, q: torch.Tensor, causal: bool) -> None:
 
 def attention_ref(q, k, v, causal: bool = True, scale: float | None = None,
                   doc: DocMask | None = None) -> torch.Tensor:
-    """fp32 reference: q [B,S,Hq,D], k/v [B,S,Hkv,D] -> [B,S,Hq,D] (q.dtype).
-    ``doc``: causal within a document (``DocMask``)."""
+    """fp32 reference (fp64 for float64 inputs): q [B,S,Hq,D], k/v [B,S,Hkv,D]
+    -> [B,S,Hq,D] (q.dtype).  ``doc``: causal within a document (``DocMask``)."""
     B, S, Hq, D = q.shape
     Hkv = k.shape[2]
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
     if doc is not None:
         _check_doc(doc, q, causal)
-    qf = q.float().transpose(1, 2)
-    kf = k.float().transpose(1, 2).repeat_interleave(Hq // Hkv, dim=1)
-    vf = v.float().transpose(1, 2).repeat_interleave(Hq // Hkv, dim=1)
+    ct = torch.float64 if q.dtype == torch.float64 else torch.float32
+    qf = q.to(ct).transpose(1, 2)
+    kf = k.to(ct).transpose(1, 2).repeat_interleave(Hq // Hkv, dim=1)
+    vf = v.to(ct).transpose(1, 2).repeat_interleave(Hq // Hkv, dim=1)
     s = qf @ kf.transpose(-1, -2) * scale
     if causal:
         mask = torch.ones(S, S, dtype=torch.bool, device=q.device).triu(1)
@@ -191,6 +196,11 @@ def attention_ref(q, k, v, causal: bool = True, scale: float | None = None,
 def attn_fwd(q, k, v, causal: bool = True, scale: float | None = None, variant: int | None = None,
              doc: DocMask | None = None):
     """HIP forward: returns (o [B,S,Hq,D] bf16, lse [B,Hq,S] fp32).
+
+    ``scale`` (default ``1 / sqrt(D)``) multiplies the raw scores
+    ``s = q k^T``: ``o = softmax(scale s) v`` under the mask, and ``lse`` is
+    the natural-log ``ln sum_j exp(scale s_ij)`` of the scaled scores over the
+    visible keys - what ``attn_bwd`` takes back with the same ``scale``.
 
     ``doc`` (a ``DocMask``): causal within a document, on the DOC form of
     variant 4 (``mxk_attn_fwd_doc``); it cannot be combined with ``variant``.
