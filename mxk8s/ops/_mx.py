@@ -1,0 +1,114 @@
+"""What the block-scaled (OCP MX) ops share: ``mxfp8.py`` and ``mxfp4.py`` keep
+their docstrings, constants and element codecs and call into here."""
+from __future__ import annotations
+
+from typing import Callable
+
+import torch
+
+from . import _lib
+
+BLOCK = 32          # elements per scale
+TILE_M = TILE_N = 256
+
+
+def check_x(x: torch.Tensor) -> None:
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("x must be a tensor")
+    if x.dtype != torch.bfloat16:
+        raise TypeError(f"x must be bfloat16, got {x.dtype}")
+    if x.dim() != 2:
+        raise ValueError(f"x must be 2-D, got shape {tuple(x.shape)}")
+    if x.shape[0] == 0 or x.shape[1] == 0 or x.shape[1] % BLOCK:
+        raise ValueError(f"x must be [R, K] with R > 0 and K a positive multiple of {BLOCK}, "
+                         f"got {tuple(x.shape)}")
+    if x.stride(1) != 1:
+        raise ValueError("x must be K-contiguous (stride(1) == 1)")
+
+
+def block_exponent(xb: torch.Tensor, emax: int) -> torch.Tensor:
+    """``xb`` fp32 ``[R, K/32, 32]`` -> int32 ``[R, K/32]``: ``floor(log2(amax)) -
+    emax`` clamped to [-127, 127], 0 for an all-zero block."""
+    amax = xb.abs().amax(dim=2)
+    _, ex = torch.frexp(amax)                     # amax = m 2^ex, m in [0.5, 1)
+    e = (ex.to(torch.int32) - 1 - emax).clamp(-127, 127)
+    return torch.where(amax == 0, torch.zeros_like(e), e)
+
+
+def check_pair(q: torch.Tensor, s: torch.Tensor, qn: str, sn: str, dtype: torch.dtype, wording: str,
+               per_byte: int) -> None:
+    """``q`` holds ``per_byte`` elements in each item of ``dtype``; ``wording``
+    names that dtype in the error."""
+    if q.dtype != dtype:
+        raise TypeError(f"{qn} must be {wording}, got {q.dtype}")
+    if s.dtype != torch.uint8:
+        raise TypeError(f"{sn} must be uint8 (E8M0 bytes), got {s.dtype}")
+    if q.dim() != 2 or s.dim() != 2:
+        raise ValueError(f"{qn} and {sn} must be 2-D, got {tuple(q.shape)} and {tuple(s.shape)}")
+    K = per_byte * q.shape[1]
+    if K % BLOCK:
+        raise ValueError(f"{qn}: K = {K} is not a multiple of {BLOCK}")
+    if tuple(s.shape) != (q.shape[0], K // BLOCK):
+        raise ValueError(f"{sn} must be [{q.shape[0]}, {K // BLOCK}], got {tuple(s.shape)}")
+    if K and (q.stride(1) != 1 or s.stride(1) != 1):
+        raise ValueError(f"{qn} and {sn} must be K-contiguous (stride(1) == 1)")
+    if q.device != s.device:
+        raise ValueError(f"{qn} and {sn} are on different devices")
+
+
+def is_fast_shape(M: int, N: int, K: int, tile_k: int) -> bool:
+    return M > 0 and N > 0 and K > 0 and M % TILE_M == 0 and N % TILE_N == 0 and K % tile_k == 0
+
+
+def check_layout(q: torch.Tensor, s: torch.Tensor, qn: str, sn: str, tile_k: int) -> None:
+    # the kernel stages elements in 16-B pieces and 4 scales as one dword
+    if q.stride(0) % 16 or q.data_ptr() % 16:
+        raise ValueError(f"{qn}: base and row stride must be multiples of 16 bytes")
+    if s.stride(0) % 4 or s.data_ptr() % 4:
+        raise ValueError(f"{sn}: base and row stride must be multiples of 4 bytes "
+                         f"(slice K at multiples of {tile_k})")
+
+
+def gemm_tn(name: str, tile_k: int, per_byte: int, check: Callable, dequantize: Callable,
+            aq: torch.Tensor, a_s: torch.Tensor, bq: torch.Tensor, b_s: torch.Tensor,
+            out: torch.Tensor | None) -> torch.Tensor:
+    """``gemm_<name>_tn``: ``check(q, s, qn, sn)`` is the format's pair check,
+    ``dequantize`` its reference, the kernel ``mxk_gemm_<name>_tn``."""
+    check(aq, a_s, "aq", "a_s")
+    check(bq, b_s, "bq", "b_s")
+    M, K = aq.shape[0], per_byte * aq.shape[1]
+    N, K2 = bq.shape[0], per_byte * bq.shape[1]
+    if K != K2:
+        raise ValueError(f"K mismatch: aq holds K = {K}, bq K = {K2}")
+    if not is_fast_shape(M, N, K, tile_k):
+        raise ValueError(f"gemm_{name}_tn needs M % {TILE_M} == 0, N % {TILE_N} == 0 and "
+                         f"K % {tile_k} == 0 (all positive), got M={M} N={N} K={K}")
+    if aq.device != bq.device:
+        raise ValueError("aq and bq are on different devices")
+    if out is not None:
+        if out.dtype != torch.bfloat16:
+            raise TypeError(f"out must be bfloat16, got {out.dtype}")
+        if out.dim() != 2 or tuple(out.shape) != (M, N):
+            raise ValueError(f"out must be [{M}, {N}]")
+        if out.stride(1) != 1:
+            raise ValueError("out must be row-major (stride(1) == 1)")
+        if out.device != aq.device:
+            raise ValueError("out is on a different device")
+    if aq.device.type == "cpu":
+        ref = (dequantize(aq, a_s) @ dequantize(bq, b_s).t()).to(torch.bfloat16)
+        if out is not None:
+            out.copy_(ref)
+            return out
+        return ref
+    check_layout(aq, a_s, "aq", "a_s", tile_k)
+    check_layout(bq, b_s, "bq", "b_s", tile_k)
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.bfloat16, device=aq.device)
+    elif out.stride(0) % 8 or out.data_ptr() % 16:
+        raise ValueError("out: base must be 16-byte aligned and the row stride a multiple of 8")
+    fn = f"mxk_gemm_{name}_tn"
+    st = getattr(_lib.lib(), fn)(aq.data_ptr(), a_s.data_ptr(), bq.data_ptr(), b_s.data_ptr(),
+                                 out.data_ptr(), M, N, K, aq.stride(0), a_s.stride(0), bq.stride(0),
+                                 b_s.stride(0), out.stride(0), _lib.stream_ptr(aq.device))
+    _lib.check(st, fn)
+    return out

@@ -34,12 +34,11 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib
+from . import _lib, _mx
+from ._mx import BLOCK, TILE_M, TILE_N  # noqa: F401  (this module's constants, as before)
 
-BLOCK = 32          # elements per scale
 E2M1_MAX = 6.0
 E2M1_EMAX = 2
-TILE_M = TILE_N = 256
 TILE_K = 256
 
 # magnitude of code 0..7
@@ -48,20 +47,6 @@ _E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
 # midpoint itself counts only where the upper neighbour is even
 _E2M1_MIDPOINTS = ((0.25, False), (0.75, True), (1.25, False), (1.75, True), (2.5, False),
                    (3.5, True), (5.0, False))
-
-
-def _check_x(x: torch.Tensor) -> None:
-    if not isinstance(x, torch.Tensor):
-        raise TypeError("x must be a tensor")
-    if x.dtype != torch.bfloat16:
-        raise TypeError(f"x must be bfloat16, got {x.dtype}")
-    if x.dim() != 2:
-        raise ValueError(f"x must be 2-D, got shape {tuple(x.shape)}")
-    if x.shape[0] == 0 or x.shape[1] == 0 or x.shape[1] % BLOCK:
-        raise ValueError(f"x must be [R, K] with R > 0 and K a positive multiple of {BLOCK}, "
-                         f"got {tuple(x.shape)}")
-    if x.stride(1) != 1:
-        raise ValueError("x must be K-contiguous (stride(1) == 1)")
 
 
 def _to_e2m1(y: torch.Tensor) -> torch.Tensor:
@@ -77,13 +62,10 @@ def _to_e2m1(y: torch.Tensor) -> torch.Tensor:
 def quantize_mxfp4_ref(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     """Pure-torch MXFP4 quantiser (any device): the definition the kernel is
     bit-identical to.  Finite inputs only."""
-    _check_x(x)
+    _mx.check_x(x)
     R, K = x.shape
     xb = x.float().reshape(R, K // BLOCK, BLOCK)
-    amax = xb.abs().amax(dim=2)
-    _, ex = torch.frexp(amax)                     # amax = m 2^ex, m in [0.5, 1)
-    e = (ex.to(torch.int32) - 1 - E2M1_EMAX).clamp(-127, 127)
-    e = torch.where(amax == 0, torch.zeros_like(e), e)
+    e = _mx.block_exponent(xb, E2M1_EMAX)
     y = torch.ldexp(xb, -e.unsqueeze(2)).clamp(-E2M1_MAX, E2M1_MAX)
     code = _to_e2m1(y).reshape(R, K // 2, 2)
     q = code[:, :, 0] | (code[:, :, 1] << 4)
@@ -94,7 +76,7 @@ def quantize_mxfp4_ref(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
 def quantize_mxfp4(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     """bf16 ``[R, K]`` -> (packed e2m1 uint8 ``[R, K/2]``, uint8 E8M0 scales
     ``[R, K/32]``).  Finite inputs only.  A row stride larger than K is fine."""
-    _check_x(x)
+    _mx.check_x(x)
     if x.device.type == "cpu":
         return quantize_mxfp4_ref(x)
     R, K = x.shape
@@ -107,21 +89,7 @@ def quantize_mxfp4(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
 
 
 def _check_pair(q: torch.Tensor, s: torch.Tensor, qn: str, sn: str) -> None:
-    if q.dtype != torch.uint8:
-        raise TypeError(f"{qn} must be uint8 (two e2m1 codes per byte), got {q.dtype}")
-    if s.dtype != torch.uint8:
-        raise TypeError(f"{sn} must be uint8 (E8M0 bytes), got {s.dtype}")
-    if q.dim() != 2 or s.dim() != 2:
-        raise ValueError(f"{qn} and {sn} must be 2-D, got {tuple(q.shape)} and {tuple(s.shape)}")
-    K = 2 * q.shape[1]
-    if K % BLOCK:
-        raise ValueError(f"{qn}: K = {K} is not a multiple of {BLOCK}")
-    if tuple(s.shape) != (q.shape[0], K // BLOCK):
-        raise ValueError(f"{sn} must be [{q.shape[0]}, {K // BLOCK}], got {tuple(s.shape)}")
-    if K and (q.stride(1) != 1 or s.stride(1) != 1):
-        raise ValueError(f"{qn} and {sn} must be K-contiguous (stride(1) == 1)")
-    if q.device != s.device:
-        raise ValueError(f"{qn} and {sn} are on different devices")
+    _mx.check_pair(q, s, qn, sn, torch.uint8, "uint8 (two e2m1 codes per byte)", 2)
 
 
 def dequantize_mxfp4(q: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
@@ -136,16 +104,7 @@ def dequantize_mxfp4(q: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
 
 
 def is_fast_shape_mxfp4(M: int, N: int, K: int) -> bool:
-    return M > 0 and N > 0 and K > 0 and M % TILE_M == 0 and N % TILE_N == 0 and K % TILE_K == 0
-
-
-def _check_layout(q: torch.Tensor, s: torch.Tensor, qn: str, sn: str) -> None:
-    # the kernel stages elements in 16-B pieces and a K-tile's 8 scales as two dwords
-    if q.stride(0) % 16 or q.data_ptr() % 16:
-        raise ValueError(f"{qn}: base and row stride must be multiples of 16 bytes")
-    if s.stride(0) % 4 or s.data_ptr() % 4:
-        raise ValueError(f"{sn}: base and row stride must be multiples of 4 bytes "
-                         "(slice K at multiples of 256)")
+    return _mx.is_fast_shape(M, N, K, TILE_K)
 
 
 def gemm_mxfp4_tn(aq: torch.Tensor, a_s: torch.Tensor, bq: torch.Tensor, b_s: torch.Tensor,
@@ -157,41 +116,4 @@ def gemm_mxfp4_tn(aq: torch.Tensor, a_s: torch.Tensor, bq: torch.Tensor, b_s: to
     of 256.  Row strides may exceed the logical widths (views into wider
     buffers, K slices of ``q`` with the matching column slice of ``s``) as
     long as element rows stay 16-byte and scale rows 4-byte aligned."""
-    _check_pair(aq, a_s, "aq", "a_s")
-    _check_pair(bq, b_s, "bq", "b_s")
-    M, K = aq.shape[0], 2 * aq.shape[1]
-    N, K2 = bq.shape[0], 2 * bq.shape[1]
-    if K != K2:
-        raise ValueError(f"K mismatch: aq holds K = {K}, bq K = {K2}")
-    if not is_fast_shape_mxfp4(M, N, K):
-        raise ValueError(f"gemm_mxfp4_tn needs M % {TILE_M} == 0, N % {TILE_N} == 0 and "
-                         f"K % {TILE_K} == 0 (all positive), got M={M} N={N} K={K}")
-    if aq.device != bq.device:
-        raise ValueError("aq and bq are on different devices")
-    if out is not None:
-        if out.dtype != torch.bfloat16:
-            raise TypeError(f"out must be bfloat16, got {out.dtype}")
-        if out.dim() != 2 or tuple(out.shape) != (M, N):
-            raise ValueError(f"out must be [{M}, {N}]")
-        if out.stride(1) != 1:
-            raise ValueError("out must be row-major (stride(1) == 1)")
-        if out.device != aq.device:
-            raise ValueError("out is on a different device")
-    if aq.device.type == "cpu":
-        ref = (dequantize_mxfp4(aq, a_s) @ dequantize_mxfp4(bq, b_s).t()).to(torch.bfloat16)
-        if out is not None:
-            out.copy_(ref)
-            return out
-        return ref
-    _check_layout(aq, a_s, "aq", "a_s")
-    _check_layout(bq, b_s, "bq", "b_s")
-    if out is None:
-        out = torch.empty((M, N), dtype=torch.bfloat16, device=aq.device)
-    elif out.stride(0) % 8 or out.data_ptr() % 16:
-        raise ValueError("out: base must be 16-byte aligned and the row stride a multiple of 8")
-    st = _lib.lib().mxk_gemm_mxfp4_tn(aq.data_ptr(), a_s.data_ptr(), bq.data_ptr(), b_s.data_ptr(),
-                                      out.data_ptr(), M, N, K, aq.stride(0), a_s.stride(0),
-                                      bq.stride(0), b_s.stride(0), out.stride(0),
-                                      _lib.stream_ptr(aq.device))
-    _lib.check(st, "mxk_gemm_mxfp4_tn")
-    return out
+    return _mx.gemm_tn("mxfp4", TILE_K, 2, _check_pair, dequantize_mxfp4, aq, a_s, bq, b_s, out)

@@ -34,10 +34,15 @@
 // lane index is the row of C and each lane owns runs of 4 consecutive columns.
 //
 // ---- structure --------------------------------------------------------------
-// The MXFP8 kernel's (gemm_mxfp8.hip), byte for byte: 256x256 output tile, 4
-// waves (2 x 2, 128x128 each = 4 x 4 MFMA blocks), K-tile of 256 elements =
-// 128 B per row, the same LDS image (LDS-DMA, 16-B chunks XOR-swizzled by
-// (row >> 1) & 7), two stages, one barrier per K-tile.  A K-tile is four MFMA
+// The tile of mx_gemm_core.h, which the MXFP8 kernel (gemm_mxfp8.hip) shares:
+// 256x256 output tile, 4 waves (2 x 2, 128x128 each = 4 x 4 MFMA blocks),
+// K-tile of 256 elements = 128 B per row, LDS image (LDS-DMA, 16-B chunks
+// XOR-swizzled by (row >> 1) & 7), two stages, one barrier per K-tile.  That
+// header holds the staging (LDS-DMA descriptor), barrier and epilogue-store
+// helpers, the validation and launch of the entry points and the quantiser's
+// quarter-block routine, once for both formats; this file keeps the format,
+// the kernel with its K-tile, MFMA, fragment and scale helpers, and the entry
+// points.  A K-tile is four MFMA
 // k-steps of 64; each costs half the matrix-core time of an e4m3 k-step, so
 // they are issued in pairs and a pair stands where the MXFP8 kernel has one
 // k-step:
@@ -50,59 +55,31 @@
 // reads.  The 8 scale bytes of a row's K-tile are two dwords (pair 0, pair 1),
 // staged by two 4-B LDS-DMAs per wave and operand into two 1 KiB planes beside
 // the tile.  Two 68 KiB stages.  The MFMAs are the compiler builtin: it places
-// the hazard waits and the accumulators.  The staging, barrier and store
-// helpers repeat those of gemm_mxfp8.hip on purpose: that file's kernels stay
-// exactly as they are measured, and the two K loops differ in every phase.
-#include "mx_common.h"
+// the hazard waits and the accumulators.
+#include "mx_gemm_core.h"
 #include "mxfp4_format.h"
 
 namespace {
 
-constexpr int kBM = 256, kBN = 256, kBK = 256;
-constexpr int kRowBytes = kBK / 2;               // 128 B of a row per K-tile
-constexpr int kThreads = 256;
-constexpr int kOpBytes = 256 * kRowBytes;        // 32 KiB per operand per stage
-constexpr int kScaleOff = 2 * kOpBytes;          // A pair 0, A pair 1, B pair 0, B pair 1 (1 KiB each)
-constexpr int kStageBytes = 2 * kOpBytes + 4096; // 68 KiB
-constexpr int kDmaPerStage = 20;                 // vector-memory ops per wave and stage
-
-typedef int i32x8_t __attribute__((ext_vector_type(8)));
-typedef int i32x4_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void lds_void_t;
+using namespace mxk::mx;
 
 // ---------------------------------------------------------------------------
 // Quantiser
 // ---------------------------------------------------------------------------
-// 8 consecutive elements of an MX block (4 dwords of two bf16 each, memory
-// order) whose other 24 are in the lane's DPP quad: the 8 e2m1 nibbles in
-// memory order; returns the block's exponent.  Every lane of the quad must be
-// active.
-__device__ __forceinline__ int quantize_quarter(const uint32_t (&w)[4], uint32_t& out) {
-  float f[8];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    f[2 * i] = __uint_as_float(w[i] << 16);
-    f[2 * i + 1] = __uint_as_float(w[i] & 0xFFFF0000u);
-  }
-  float amax = 0.f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) amax = fmaxf(amax, fabsf(f[i]));
-  // the block's other three lanes: quad_perm [1,0,3,2] then [2,3,0,1]
-  amax = fmaxf(amax, __uint_as_float(__builtin_amdgcn_mov_dpp(__float_as_uint(amax), 0xB1, 0xF, 0xF, true)));
-  amax = fmaxf(amax, __uint_as_float(__builtin_amdgcn_mov_dpp(__float_as_uint(amax), 0x4E, 0xF, 0xF, true)));
-  const int e = mxfp4::block_exp(amax);
-  const float inv = mxfp4::block_inv_scale(e);
-  out = 0;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const float v = fminf(fmaxf(f[i] * inv, -mxfp4::kMax), mxfp4::kMax);   // explicit saturation
-    out |= mxfp4::f32_to_e2m1(v) << (4 * i);
-  }
-  return e;
-}
+// The element format of the shared quantiser (mx_gemm_core.h): one packed
+// dword per lane.
+struct E2m1 {
+  static constexpr int kBits = 4;
+  static constexpr float kMax = mxfp4::kMax;
+  __device__ static int block_exp(float amax) { return mxfp4::block_exp(amax); }
+  __device__ static float inv_scale(int e) { return mxfp4::block_inv_scale(e); }
+  __device__ static uint32_t convert(float v) { return mxfp4::f32_to_e2m1(v); }
+};
 
 // One lane per 8 consecutive elements (one packed dword), 4 lanes (a DPP quad)
-// per MX block.
+// per MX block.  The body is its own copy in either format's file: written
+// once as a function that both kernels call, it compiles to other by-element
+// kernels.
 template <bool VEC>
 __global__ void __launch_bounds__(256)
 quantize_mxfp4_kernel(const uint16_t* __restrict__ x, uint8_t* __restrict__ q,
@@ -122,14 +99,14 @@ quantize_mxfp4_kernel(const uint16_t* __restrict__ x, uint8_t* __restrict__ q,
 #pragma unroll
     for (int i = 0; i < 4; ++i) w[i] = xp[2 * i] | (static_cast<uint32_t>(xp[2 * i + 1]) << 16);
   }
-  uint32_t out;
-  const int e = quantize_quarter(w, out);
+  uint32_t out[1];
+  const int e = quantize_quarter<E2m1>(w, out);
   uint8_t* qp = q + row * ldq + c8 * 4;
   if constexpr (VEC) {
-    *reinterpret_cast<uint32_t*>(qp) = out;
+    store_quarter<E2m1>(qp, out);
   } else {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) qp[i] = static_cast<uint8_t>(out >> (8 * i));
+    for (int i = 0; i < 4; ++i) qp[i] = static_cast<uint8_t>(out[i >> 2] >> (8 * (i & 3)));
   }
   if ((c8 & 3) == 0) s[row * lds + (c8 >> 2)] = static_cast<uint8_t>(e + 127);
 }
@@ -137,52 +114,11 @@ quantize_mxfp4_kernel(const uint16_t* __restrict__ x, uint8_t* __restrict__ q,
 // ---------------------------------------------------------------------------
 // GEMM
 // ---------------------------------------------------------------------------
-// LDS-DMA descriptor of one 256-row operand panel (bytes) and of its scale
-// rows.
-struct Dma4 {
-  __amdgpu_buffer_rsrc_t rsrc;    // 256 rows of ld bytes
-  __amdgpu_buffer_rsrc_t srsrc;   // 256 rows of lds scale bytes
-  uint32_t voff;                  // row lane >> 3 of a piece, swizzled 16-B chunk
-  uint32_t svoff;                 // first scale dword of row 64 wave + lane
-  int piece;                      // bytes between pieces (32 rows), scalar
-  int wave_off;                   // this wave's 8 rows inside a piece, scalar
-  // piece p: rows (4p + wave) 8 .. + 8; the row part rides in the scalar offset.
-  // lds_sc: the operand's two scale planes (pair 0, pair 1), 1 KiB each.
-  __device__ __forceinline__ void issue(char* lds_op, char* lds_sc, int k_bytes, int wave) const {
-#pragma unroll
-    for (int p = 0; p < 8; ++p)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_t*)(lds_op + (p * 4 + wave) * 1024),
-                                               16, voff, k_bytes + wave_off + p * piece, 0, 0);
-    // k_bytes >> 4: 16 packed bytes per scale byte
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(srsrc, (lds_void_t*)(lds_sc + wave * 256), 4, svoff,
-                                             k_bytes >> 4, 0, 0);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(srsrc, (lds_void_t*)(lds_sc + 1024 + wave * 256), 4,
-                                             svoff, (k_bytes >> 4) + 4, 0, 0);
-  }
-};
-
-__device__ __forceinline__ Dma4 make_dma4(const uint8_t* q, const uint8_t* sc, int ld, int lds,
-                                          int row0, int lane, int wave) {
-  Dma4 d;
-  d.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(q + static_cast<size_t>(row0) * ld),
-                                             0, 256 * ld, 0x00020000);
-  d.srsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint8_t*>(sc + static_cast<size_t>(row0) * lds), 0, 256 * lds, 0x00020000);
-  const int r = lane >> 3;
-  const int c = (lane & 7) ^ ((4 * (wave & 1) + (r >> 1)) & 7);
-  d.voff = static_cast<uint32_t>(r * ld + c * 16);
-  d.piece = 32 * ld;
-  d.wave_off = wave * 8 * ld;
-  d.svoff = static_cast<uint32_t>((wave * 64 + lane) * lds);
-  return d;
-}
-
-// Fragment byte offsets of this lane inside a 32-row block: pair p takes the
-// 16-B chunks 4 p + (lane >> 5) (its first k-step) and 4 p + 2 + (lane >> 5)
-// (its second) of row lane & 31.
-struct FragOff {
-  int lo[2], hi[2];
-};
+constexpr int kBK = 256;   // elements per K-tile: 128 B of a row
+// two scale dwords (pair 0, pair 1) per row and K-tile, 16 packed bytes per scale byte
+using Dma4 = Dma<2, 4>;
+constexpr int kStageBytes = 2 * kOpBytes + 4096; // 68 KiB: A pair 0, A pair 1, B pair 0, B pair 1 (1 KiB each)
+constexpr int kDmaPerStage = 20;                 // vector-memory ops per wave and stage
 
 // One pair of k-steps: per 32-row block the lane's operand of the first
 // (lo) and second (hi) k-step.
@@ -248,13 +184,6 @@ __device__ __forceinline__ void read_scales(Scales& s, const char* stage, int a_
   for (int j = 0; j < 4; ++j) s.b[j] = static_cast<int>(static_cast<uint32_t>(pb[j * 32]) >> shift);
 }
 
-__device__ __forceinline__ void lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ void block_barrier() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-
 // K-tile t, read from stage buffer X (Y: the other one).  DMA: stage t+2
 // exists and goes out here, at k offset kb2 bytes (every K-tile but the last
 // two).  The reads of stage t+1 are unconditional: in the last K-tile they
@@ -315,41 +244,6 @@ __device__ __forceinline__ void ktile(f32x16_t (&acc)[4][4], Frags& f0, Scales& 
   __builtin_amdgcn_sched_barrier(0);
 }
 
-// bf16 store of a wave's 128x128 block through its LDS slice, two 64-row
-// passes with 272-B padded rows, read back row-major so every global store
-// covers 4 rows x 256 B (the 32x32 C map: lane = row, register group g =
-// columns 8 g + 4 (lane >> 5) .. + 3).
-__device__ __forceinline__ void store_block32_lds(const f32x16_t (&acc)[4][4], uint16_t* C, int ldc,
-                                                  int row0, int col0, int lane, char* lds) {
-  const int r32 = lane & 31, h = lane >> 5;
-  const int rr = lane >> 4, cc = (lane & 15) * 8;
-#pragma unroll
-  for (int p = 0; p < 2; ++p) {
-#pragma unroll
-    for (int ii = 0; ii < 2; ++ii)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const f32x16_t& v = acc[2 * p + ii][j];
-          uint2 pk;
-          pk.x = mxk::pack2bf(v[4 * g], v[4 * g + 1]);
-          pk.y = mxk::pack2bf(v[4 * g + 2], v[4 * g + 3]);
-          *reinterpret_cast<uint2*>(lds + (ii * 32 + r32) * mxk::kStoreLdsRow +
-                                    (j * 32 + 8 * g + 4 * h) * 2) = pk;
-        }
-#pragma unroll
-    for (int it = 0; it < 16; ++it) {
-      const int r = it * 4 + rr;
-      const u32x4_t v = *reinterpret_cast<const u32x4_t*>(lds + r * mxk::kStoreLdsRow + cc * 2);
-      uint16_t* cp = C + static_cast<size_t>(row0 + p * 64 + r) * ldc + col0 + cc;
-      __builtin_nontemporal_store(v, reinterpret_cast<u32x4_t*>(cp));
-    }
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-    __asm__ volatile("" ::: "memory");
-  }
-}
-
 __global__ void __launch_bounds__(kThreads, 1)
 mxk_gemm_mxfp4_tn_kernel(const uint8_t* __restrict__ Aq, const uint8_t* __restrict__ As,
                          const uint8_t* __restrict__ Bq, const uint8_t* __restrict__ Bs,
@@ -362,8 +256,8 @@ mxk_gemm_mxfp4_tn_kernel(const uint8_t* __restrict__ Aq, const uint8_t* __restri
   const int wm = wave >> 1, wn = wave & 1;
   int m0, n0;
   mxk::w4b_tile<1>(blockIdx.x, gridDim.x, M / kBM, N / kBN, &m0, &n0);
-  const Dma4 dma_a = make_dma4(Aq, As, lda, ldsa, m0, lane, wave);
-  const Dma4 dma_b = make_dma4(Bq, Bs, ldb, ldsb, n0, lane, wave);
+  const Dma4 dma_a = Dma4::make(Aq, As, lda, ldsa, m0, lane, wave);
+  const Dma4 dma_b = Dma4::make(Bq, Bs, ldb, ldsb, n0, lane, wave);
   const int ns = K / kBK;
 
   const int r32 = lane & 31, h = lane >> 5;
@@ -434,38 +328,19 @@ mxk_gemm_mxfp4_tn_kernel(const uint8_t* __restrict__ Aq, const uint8_t* __restri
                     smem + wave * mxk::kStoreLdsWave);
 }
 
-bool mxfp4_shape_ok(int M, int N, int K) {
-  return M > 0 && N > 0 && K > 0 && M % kBM == 0 && N % kBN == 0 && K % kBK == 0;
-}
-
-bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 }  // namespace
 
-MXK_API int mxk_gemm_mxfp4_tn_is_fast(int M, int N, int K) { return mxfp4_shape_ok(M, N, K) ? 1 : 0; }
+MXK_API int mxk_gemm_mxfp4_tn_is_fast(int M, int N, int K) {
+  return gemm_tn_shape_ok(M, N, K, kBK) ? 1 : 0;
+}
 
-// lda / ldb: bytes between packed rows (>= K / 2).  Elements: 16-B aligned
-// base, row stride a multiple of 16 B.  Scales: 4-B aligned base, row stride a
-// multiple of 4 B (a dword carries the 4 block scales of half a K-tile).  C:
-// 16-B aligned, ldc % 8 == 0.  Row strides below 2^23.
+// The contract is gemm_tn_args_ok's (mx_gemm_core.h), two elements per byte:
+// lda / ldb count bytes between packed rows (>= K / 2).
 MXK_API int mxk_gemm_mxfp4_tn(const void* Aq, const void* As, const void* Bq, const void* Bs,
                               void* C, int M, int N, int K, int lda, int ldsa, int ldb, int ldsb,
                               int ldc, hipStream_t stream) {
-  if (!mxfp4_shape_ok(M, N, K) || !Aq || !As || !Bq || !Bs || !C)
-    return static_cast<int>(hipErrorInvalidValue);
-  constexpr int kMaxLd = 1 << 23;
-  if (lda < K / 2 || ldb < K / 2 || ldsa < K / 32 || ldsb < K / 32 || ldc < N || lda >= kMaxLd ||
-      ldb >= kMaxLd || ldsa >= kMaxLd || ldsb >= kMaxLd)
-    return static_cast<int>(hipErrorInvalidValue);
-  if (!aligned(Aq, 16) || !aligned(Bq, 16) || lda % 16 || ldb % 16 || !aligned(As, 4) ||
-      !aligned(Bs, 4) || ldsa % 4 || ldsb % 4 || !aligned(C, 16) || ldc % 8)
-    return static_cast<int>(hipErrorInvalidValue);
-  const int tiles = (M / kBM) * (N / kBN);
-  hipLaunchKernelGGL(mxk_gemm_mxfp4_tn_kernel, dim3(tiles), dim3(kThreads), 0, stream,
-                     static_cast<const uint8_t*>(Aq), static_cast<const uint8_t*>(As),
-                     static_cast<const uint8_t*>(Bq), static_cast<const uint8_t*>(Bs),
-                     static_cast<uint16_t*>(C), M, N, K, lda, ldsa, ldb, ldsb, ldc);
-  MXK_RETURN_LAUNCH_STATUS();
+  return launch_gemm_tn<kBK>(mxk_gemm_mxfp4_tn_kernel, Aq, As, Bq, Bs, C, M, N, K, lda, ldsa, ldb, ldsb,
+                               ldc, stream);
 }
 
 // x: bf16 [R][K] (row stride ldx elements), K % 32 == 0, finite values only.
@@ -473,20 +348,6 @@ MXK_API int mxk_gemm_mxfp4_tn(const void* Aq, const void* As, const void* Bq, co
 // [R][K / 32] (row stride lds).  The definition is in mxfp4_format.h.
 MXK_API int mxk_quantize_mxfp4(const void* x, void* q, void* s, long R, int K, long ldx, long ldq,
                                long lds, hipStream_t stream) {
-  if (!x || !q || !s || R <= 0 || K <= 0 || K % 32 || ldx < K || ldq < K / 2 || lds < K / 32)
-    return static_cast<int>(hipErrorInvalidValue);
-  const long lanes = R * (K / 8);
-  const long blocks = (lanes + 255) / 256;
-  if (blocks > 0x7FFFFFFFL) return static_cast<int>(hipErrorInvalidValue);
-  // 16-B loads of x, 4-B stores of q: everything else goes by element
-  const bool vec = aligned(x, 16) && ldx % 8 == 0 && aligned(q, 4) && ldq % 4 == 0;
-  if (vec)
-    hipLaunchKernelGGL(quantize_mxfp4_kernel<true>, dim3(static_cast<unsigned>(blocks)), dim3(256), 0,
-                       stream, static_cast<const uint16_t*>(x), static_cast<uint8_t*>(q),
-                       static_cast<uint8_t*>(s), R, K, ldx, ldq, lds);
-  else
-    hipLaunchKernelGGL(quantize_mxfp4_kernel<false>, dim3(static_cast<unsigned>(blocks)), dim3(256), 0,
-                       stream, static_cast<const uint16_t*>(x), static_cast<uint8_t*>(q),
-                       static_cast<uint8_t*>(s), R, K, ldx, ldq, lds);
-  MXK_RETURN_LAUNCH_STATUS();
+  return launch_quantize_rows<E2m1>(quantize_mxfp4_kernel<true>, quantize_mxfp4_kernel<false>, x, q, s,
+                                    R, K, ldx, ldq, lds, stream);
 }

@@ -40,83 +40,58 @@
 //                     and scales of stage t+1
 // so a stage has one whole K-tile to land.  The MFMAs are the compiler
 // builtin: it places the hazard waits and the accumulators.
-#include "mx_common.h"
+#include "mx_gemm_core.h"
 
 namespace {
 
-constexpr int kBM = 256, kBN = 256, kBK = 128;
-constexpr int kThreads = 256;
-constexpr int kOpBytes = 256 * 128;              // 32 KiB per operand per stage
-constexpr int kScaleOff = 2 * kOpBytes;          // A scales, then B scales (1 KiB each)
-constexpr int kStageBytes = 2 * kOpBytes + 2048; // 66 KiB
-constexpr int kDmaPerStage = 18;                 // vector-memory ops per wave and stage
-
-typedef int i32x8_t __attribute__((ext_vector_type(8)));
-typedef int i32x4_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void lds_void_t;
+using namespace mxk::mx;
 
 // ---------------------------------------------------------------------------
 // Quantiser
 // ---------------------------------------------------------------------------
-// RNE of a finite fp32 with |v| <= 448 to an e4m3fn byte.
-__host__ __device__ inline uint32_t f32_to_e4m3(float v) {
-  uint32_t u;
-  __builtin_memcpy(&u, &v, 4);
-  const uint32_t sign = (u >> 24) & 0x80u;
-  u &= 0x7FFFFFFFu;
-  uint32_t r;
-  if (u >= 0x3C800000u) {                 // >= 2^-6: a normal e4m3
-    u += 0x7FFFFu + ((u >> 20) & 1u);     // round to 3 mantissa bits, ties to even
-    r = (u >> 20) - (120u << 3);          // rebias 127 -> 7
-  } else {                                // subnormal: units of 2^-9
-    float a;
-    __builtin_memcpy(&a, &u, 4);
-    a += 16384.0f;                        // 2^14: the sum's last bit is 2^-9
-    uint32_t b;
-    __builtin_memcpy(&b, &a, 4);
-    r = b - 0x46800000u;
-  }
-  return r | sign;
-}
+// The element format of the shared quantiser (mx_gemm_core.h).
+struct E4m3 {
+  static constexpr int kBits = 8;
+  static constexpr float kMax = 448.f;
 
-// floor(log2(amax)) - 8 clamped to [-127, 127]; 0 for amax == 0
-__host__ __device__ inline int mx_block_exp(float amax) {
-  uint32_t u;
-  __builtin_memcpy(&u, &amax, 4);
-  if (u == 0) return 0;
-  const int e = static_cast<int>(u >> 23) - 127 - 8;   // an fp32 subnormal lands below -127
-  return e < -127 ? -127 : e;                           // bf16 input: e <= 119
-}
-
-// 8 consecutive elements of an MX block (4 dwords of two bf16 each, memory
-// order) whose other 24 are in the lane's DPP quad: the 8 e4m3 bytes in
-// memory order; returns the block's exponent.  Every lane of the quad must be
-// active.
-__device__ __forceinline__ int quantize_quarter(const uint32_t (&w)[4], uint32_t (&out)[2]) {
-  float f[8];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    f[2 * i] = __uint_as_float(w[i] << 16);
-    f[2 * i + 1] = __uint_as_float(w[i] & 0xFFFF0000u);
+  // floor(log2(amax)) - 8 clamped to [-127, 127]; 0 for amax == 0
+  __device__ static int block_exp(float amax) {
+    uint32_t u;
+    __builtin_memcpy(&u, &amax, 4);
+    if (u == 0) return 0;
+    const int e = static_cast<int>(u >> 23) - 127 - 8;   // an fp32 subnormal lands below -127
+    return e < -127 ? -127 : e;                           // bf16 input: e <= 119
   }
-  float amax = 0.f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) amax = fmaxf(amax, fabsf(f[i]));
-  // the block's other three lanes: quad_perm [1,0,3,2] then [2,3,0,1]
-  amax = fmaxf(amax, __uint_as_float(__builtin_amdgcn_mov_dpp(__float_as_uint(amax), 0xB1, 0xF, 0xF, true)));
-  amax = fmaxf(amax, __uint_as_float(__builtin_amdgcn_mov_dpp(__float_as_uint(amax), 0x4E, 0xF, 0xF, true)));
-  const int e = mx_block_exp(amax);
-  const float inv = __uint_as_float(static_cast<uint32_t>(127 - e) << 23);   // 2^-e
-  out[0] = out[1] = 0;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const float v = fminf(fmaxf(f[i] * inv, -448.f), 448.f);   // explicit saturation
-    out[i >> 2] |= f32_to_e4m3(v) << (8 * (i & 3));
-  }
-  return e;
-}
 
-// One lane per 8 consecutive elements, 4 lanes (a DPP quad) per MX block.
+  __device__ static float inv_scale(int e) {   // 2^-e
+    return __uint_as_float(static_cast<uint32_t>(127 - e) << 23);
+  }
+
+  // RNE of a finite fp32 with |v| <= 448 to an e4m3fn byte.
+  __device__ static uint32_t convert(float v) {
+    uint32_t u;
+    __builtin_memcpy(&u, &v, 4);
+    const uint32_t sign = (u >> 24) & 0x80u;
+    u &= 0x7FFFFFFFu;
+    uint32_t r;
+    if (u >= 0x3C800000u) {                 // >= 2^-6: a normal e4m3
+      u += 0x7FFFFu + ((u >> 20) & 1u);     // round to 3 mantissa bits, ties to even
+      r = (u >> 20) - (120u << 3);          // rebias 127 -> 7
+    } else {                                // subnormal: units of 2^-9
+      float a;
+      __builtin_memcpy(&a, &u, 4);
+      a += 16384.0f;                        // 2^14: the sum's last bit is 2^-9
+      uint32_t b;
+      __builtin_memcpy(&b, &a, 4);
+      r = b - 0x46800000u;
+    }
+    return r | sign;
+  }
+};
+
+// One lane per 8 consecutive elements, 4 lanes (a DPP quad) per MX
+// block.  The body is its own copy in either format's file: written once as a
+// function that both kernels call, it compiles to other by-element kernels.
 template <bool VEC>
 __global__ void __launch_bounds__(256)
 quantize_mxfp8_kernel(const uint16_t* __restrict__ x, uint8_t* __restrict__ q,
@@ -137,10 +112,10 @@ quantize_mxfp8_kernel(const uint16_t* __restrict__ x, uint8_t* __restrict__ q,
     for (int i = 0; i < 4; ++i) w[i] = xp[2 * i] | (static_cast<uint32_t>(xp[2 * i + 1]) << 16);
   }
   uint32_t out[2];
-  const int e = quantize_quarter(w, out);
+  const int e = quantize_quarter<E4m3>(w, out);
   uint8_t* qp = q + row * ldq + c8 * 8;
   if constexpr (VEC) {
-    *reinterpret_cast<uint2*>(qp) = make_uint2(out[0], out[1]);
+    store_quarter<E4m3>(qp, out);
   } else {
 #pragma unroll
     for (int i = 0; i < 8; ++i) qp[i] = static_cast<uint8_t>(out[i >> 2] >> (8 * (i & 3)));
@@ -206,11 +181,11 @@ quantize_mxfp8_tr_kernel(const uint16_t* __restrict__ x, uint8_t* __restrict__ q
       }
       if constexpr (DUAL) {
         uint32_t out[2];
-        const int e = quantize_quarter(w[h], out);
+        const int e = quantize_quarter<E4m3>(w[h], out);
         if (row < R && col < C) {   // C % 32 == 0: whole blocks
           uint8_t* qp = q + row * ldq + col;
           if constexpr (VEC) {
-            *reinterpret_cast<uint2*>(qp) = make_uint2(out[0], out[1]);
+            store_quarter<E4m3>(qp, out);
           } else {
 #pragma unroll
             for (int i = 0; i < 8; ++i) qp[i] = static_cast<uint8_t>(out[i >> 2] >> (8 * (i & 3)));
@@ -238,12 +213,12 @@ quantize_mxfp8_tr_kernel(const uint16_t* __restrict__ x, uint8_t* __restrict__ q
     const uint2 b = *reinterpret_cast<const uint2*>(tp + 8);
     const uint32_t w[4] = {a.x, a.y, b.x, b.y};
     uint32_t out[2];
-    const int e = quantize_quarter(w, out);
+    const int e = quantize_quarter<E4m3>(w, out);
     const long c = c0 + cl;
     if (row < R && c < C) {   // R % 32 == 0: whole blocks
       uint8_t* qp = qt + c * ldqt + row;
       if constexpr (VEC) {
-        *reinterpret_cast<uint2*>(qp) = make_uint2(out[0], out[1]);
+        store_quarter<E4m3>(qp, out);
       } else {
 #pragma unroll
         for (int i = 0; i < 8; ++i) qp[i] = static_cast<uint8_t>(out[i >> 2] >> (8 * (i & 3)));
@@ -256,54 +231,17 @@ quantize_mxfp8_tr_kernel(const uint16_t* __restrict__ x, uint8_t* __restrict__ q
 // ---------------------------------------------------------------------------
 // GEMM
 // ---------------------------------------------------------------------------
-// LDS-DMA descriptor of one 256-row operand panel (bytes; gemm_tn_core.h DmaK
-// for 1-byte elements) and of its scale rows.
-struct Dma8 {
-  __amdgpu_buffer_rsrc_t rsrc;    // 256 rows of ld bytes
-  __amdgpu_buffer_rsrc_t srsrc;   // 256 rows of lds scale bytes
-  uint32_t voff;                  // row lane >> 3 of a piece, swizzled 16-B chunk
-  uint32_t svoff;                 // scale dword of row 64 wave + lane
-  int piece;                      // bytes between pieces (32 rows), scalar
-  int wave_off;                   // this wave's 8 rows inside a piece, scalar
-  // piece p: rows (4p + wave) 8 .. + 8; the row part rides in the scalar offset
-  __device__ __forceinline__ void issue(char* lds_op, char* lds_sc, int k_bytes, int wave) const {
-#pragma unroll
-    for (int p = 0; p < 8; ++p)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_t*)(lds_op + (p * 4 + wave) * 1024),
-                                               16, voff, k_bytes + wave_off + p * piece, 0, 0);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(srsrc, (lds_void_t*)(lds_sc + wave * 256), 4, svoff,
-                                             k_bytes >> 5, 0, 0);
-  }
-};
-
-__device__ __forceinline__ Dma8 make_dma8(const uint8_t* q, const uint8_t* sc, int ld, int lds,
-                                          int row0, int lane, int wave) {
-  Dma8 d;
-  d.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(q + static_cast<size_t>(row0) * ld),
-                                             0, 256 * ld, 0x00020000);
-  d.srsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint8_t*>(sc + static_cast<size_t>(row0) * lds), 0, 256 * lds, 0x00020000);
-  const int r = lane >> 3;
-  const int c = (lane & 7) ^ ((4 * (wave & 1) + (r >> 1)) & 7);
-  d.voff = static_cast<uint32_t>(r * ld + c * 16);
-  d.piece = 32 * ld;
-  d.wave_off = wave * 8 * ld;
-  d.svoff = static_cast<uint32_t>((wave * 64 + lane) * lds);
-  return d;
-}
+constexpr int kBK = 128;   // elements per K-tile: 128 B of a row
+// one scale dword per row and K-tile, 32 element bytes per scale byte
+using Dma8 = Dma<1, 5>;
+constexpr int kStageBytes = 2 * kOpBytes + 2048; // 66 KiB: A scales, then B scales (1 KiB each)
+constexpr int kDmaPerStage = 18;                 // vector-memory ops per wave and stage
 
 __device__ __forceinline__ i32x8_t lds_frag(const char* p, int off_lo, int off_hi) {
   const i32x4_t lo = *reinterpret_cast<const i32x4_t*>(p + off_lo);
   const i32x4_t hi = *reinterpret_cast<const i32x4_t*>(p + off_hi);
   return i32x8_t{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
 }
-
-// Fragment byte offsets of this lane inside a 32-row block: k-step ks takes
-// the 16-B chunks 4 ks + (lane >> 5) (low 4 VGPRs) and 4 ks + 2 + (lane >> 5)
-// (high 4 VGPRs) of row lane & 31.
-struct FragOff {
-  int lo[2], hi[2];
-};
 
 struct Frags {
   i32x8_t a[4], b[4];
@@ -339,13 +277,6 @@ __device__ __forceinline__ void read_scales(int (&sa)[4], int (&sb)[4], const ch
   for (int i = 0; i < 4; ++i) sa[i] = static_cast<int>(static_cast<uint32_t>(pa[i * 32]) >> shift);
 #pragma unroll
   for (int j = 0; j < 4; ++j) sb[j] = static_cast<int>(static_cast<uint32_t>(pb[j * 32]) >> shift);
-}
-
-__device__ __forceinline__ void lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ void block_barrier() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
 }
 
 // K-tile t, read from stage buffer X (Y: the other one).  DMA: stage t+2
@@ -405,41 +336,6 @@ __device__ __forceinline__ void ktile(f32x16_t (&acc)[4][4], Frags& f0, int (&sa
   }
 }
 
-// bf16 store of a wave's 128x128 block through its LDS slice, two 64-row
-// passes with 272-B padded rows, read back row-major so every global store
-// covers 4 rows x 256 B (mx_common.h store_block_lds for the 32x32 C map:
-// lane = row, register group g = columns 8 g + 4 (lane >> 5) .. + 3).
-__device__ __forceinline__ void store_block32_lds(const f32x16_t (&acc)[4][4], uint16_t* C, int ldc,
-                                                  int row0, int col0, int lane, char* lds) {
-  const int r32 = lane & 31, h = lane >> 5;
-  const int rr = lane >> 4, cc = (lane & 15) * 8;
-#pragma unroll
-  for (int p = 0; p < 2; ++p) {
-#pragma unroll
-    for (int ii = 0; ii < 2; ++ii)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const f32x16_t& v = acc[2 * p + ii][j];
-          uint2 pk;
-          pk.x = mxk::pack2bf(v[4 * g], v[4 * g + 1]);
-          pk.y = mxk::pack2bf(v[4 * g + 2], v[4 * g + 3]);
-          *reinterpret_cast<uint2*>(lds + (ii * 32 + r32) * mxk::kStoreLdsRow +
-                                    (j * 32 + 8 * g + 4 * h) * 2) = pk;
-        }
-#pragma unroll
-    for (int it = 0; it < 16; ++it) {
-      const int r = it * 4 + rr;
-      const u32x4_t v = *reinterpret_cast<const u32x4_t*>(lds + r * mxk::kStoreLdsRow + cc * 2);
-      uint16_t* cp = C + static_cast<size_t>(row0 + p * 64 + r) * ldc + col0 + cc;
-      __builtin_nontemporal_store(v, reinterpret_cast<u32x4_t*>(cp));
-    }
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-    __asm__ volatile("" ::: "memory");
-  }
-}
-
 __global__ void __launch_bounds__(kThreads, 1)
 mxk_gemm_mxfp8_tn_kernel(const uint8_t* __restrict__ Aq, const uint8_t* __restrict__ As,
                          const uint8_t* __restrict__ Bq, const uint8_t* __restrict__ Bs,
@@ -452,8 +348,8 @@ mxk_gemm_mxfp8_tn_kernel(const uint8_t* __restrict__ Aq, const uint8_t* __restri
   const int wm = wave >> 1, wn = wave & 1;
   int m0, n0;
   mxk::w4b_tile<1>(blockIdx.x, gridDim.x, M / kBM, N / kBN, &m0, &n0);
-  const Dma8 dma_a = make_dma8(Aq, As, lda, ldsa, m0, lane, wave);
-  const Dma8 dma_b = make_dma8(Bq, Bs, ldb, ldsb, n0, lane, wave);
+  const Dma8 dma_a = Dma8::make(Aq, As, lda, ldsa, m0, lane, wave);
+  const Dma8 dma_b = Dma8::make(Bq, Bs, ldb, ldsb, n0, lane, wave);
   const int ns = K / kBK;
 
   const int r32 = lane & 31, h = lane >> 5;
@@ -527,37 +423,18 @@ mxk_gemm_mxfp8_tn_kernel(const uint8_t* __restrict__ Aq, const uint8_t* __restri
                     smem + wave * mxk::kStoreLdsWave);
 }
 
-bool mxfp8_shape_ok(int M, int N, int K) {
-  return M > 0 && N > 0 && K > 0 && M % kBM == 0 && N % kBN == 0 && K % kBK == 0;
-}
-
-bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 }  // namespace
 
-MXK_API int mxk_gemm_mxfp8_tn_is_fast(int M, int N, int K) { return mxfp8_shape_ok(M, N, K) ? 1 : 0; }
+MXK_API int mxk_gemm_mxfp8_tn_is_fast(int M, int N, int K) {
+  return gemm_tn_shape_ok(M, N, K, kBK) ? 1 : 0;
+}
 
-// Elements: 16-B aligned base, row stride a multiple of 16 B.  Scales: 4-B
-// aligned base, row stride a multiple of 4 B (one dword carries a K-tile's 4
-// block scales).  C: 16-B aligned, ldc % 8 == 0.  Row strides below 2^23.
+// The contract is gemm_tn_args_ok's (mx_gemm_core.h), one element per byte.
 MXK_API int mxk_gemm_mxfp8_tn(const void* Aq, const void* As, const void* Bq, const void* Bs,
                               void* C, int M, int N, int K, int lda, int ldsa, int ldb, int ldsb,
                               int ldc, hipStream_t stream) {
-  if (!mxfp8_shape_ok(M, N, K) || !Aq || !As || !Bq || !Bs || !C)
-    return static_cast<int>(hipErrorInvalidValue);
-  constexpr int kMaxLd = 1 << 23;
-  if (lda < K || ldb < K || ldsa < K / 32 || ldsb < K / 32 || ldc < N || lda >= kMaxLd ||
-      ldb >= kMaxLd || ldsa >= kMaxLd || ldsb >= kMaxLd)
-    return static_cast<int>(hipErrorInvalidValue);
-  if (!aligned(Aq, 16) || !aligned(Bq, 16) || lda % 16 || ldb % 16 || !aligned(As, 4) ||
-      !aligned(Bs, 4) || ldsa % 4 || ldsb % 4 || !aligned(C, 16) || ldc % 8)
-    return static_cast<int>(hipErrorInvalidValue);
-  const int tiles = (M / kBM) * (N / kBN);
-  hipLaunchKernelGGL(mxk_gemm_mxfp8_tn_kernel, dim3(tiles), dim3(kThreads), 0, stream,
-                     static_cast<const uint8_t*>(Aq), static_cast<const uint8_t*>(As),
-                     static_cast<const uint8_t*>(Bq), static_cast<const uint8_t*>(Bs),
-                     static_cast<uint16_t*>(C), M, N, K, lda, ldsa, ldb, ldsb, ldc);
-  MXK_RETURN_LAUNCH_STATUS();
+  return launch_gemm_tn<kBK>(mxk_gemm_mxfp8_tn_kernel, Aq, As, Bq, Bs, C, M, N, K, lda, ldsa, ldb, ldsb,
+                               ldc, stream);
 }
 
 // x: bf16 [R][K] (row stride ldx elements), K % 32 == 0, finite values only.
@@ -566,21 +443,8 @@ MXK_API int mxk_gemm_mxfp8_tn(const void* Aq, const void* As, const void* Bq, co
 // byte e + 127 (127 for a zero block), element RNE(clamp(x 2^-e, +-448)).
 MXK_API int mxk_quantize_mxfp8(const void* x, void* q, void* s, long R, int K, long ldx, long ldq,
                                long lds, hipStream_t stream) {
-  if (!x || !q || !s || R <= 0 || K <= 0 || K % 32 || ldx < K || ldq < K || lds < K / 32)
-    return static_cast<int>(hipErrorInvalidValue);
-  const long lanes = R * (K / 8);
-  const long blocks = (lanes + 255) / 256;
-  if (blocks > 0x7FFFFFFFL) return static_cast<int>(hipErrorInvalidValue);
-  const bool vec = aligned(x, 16) && ldx % 8 == 0 && aligned(q, 8) && ldq % 8 == 0;
-  if (vec)
-    hipLaunchKernelGGL(quantize_mxfp8_kernel<true>, dim3(static_cast<unsigned>(blocks)), dim3(256), 0,
-                       stream, static_cast<const uint16_t*>(x), static_cast<uint8_t*>(q),
-                       static_cast<uint8_t*>(s), R, K, ldx, ldq, lds);
-  else
-    hipLaunchKernelGGL(quantize_mxfp8_kernel<false>, dim3(static_cast<unsigned>(blocks)), dim3(256), 0,
-                       stream, static_cast<const uint16_t*>(x), static_cast<uint8_t*>(q),
-                       static_cast<uint8_t*>(s), R, K, ldx, ldq, lds);
-  MXK_RETURN_LAUNCH_STATUS();
+  return launch_quantize_rows<E4m3>(quantize_mxfp8_kernel<true>, quantize_mxfp8_kernel<false>, x, q, s,
+                                    R, K, ldx, ldq, lds, stream);
 }
 
 namespace {
