@@ -11,6 +11,7 @@
 #   make test-native  host unit tests of libmxnode (ASan+UBSan build)
 #   make test-native-tsan  libmxnode re-entrancy test under ThreadSanitizer
 #   make test-attention-plan  the attention backward plan's sweep (host, ASan+UBSan build)
+#   make test-gemm-plan       the bf16 GEMM plans' sweep, hostile integers included (host, ASan+UBSan build)
 #   make test-attention-doc   the document-mask predicate and tile bounds (host, ASan+UBSan build)
 #   make test-mxfp4-format    the e2m1 conversion and block exponent over every bf16 (host, ASan+UBSan build)
 #
@@ -42,7 +43,7 @@ NODE_SRCS := $(wildcard native/libmxnode/*.cc)
 NODE_OBJS := $(patsubst native/libmxnode/%.cc,$(BUILD)/node/%.o,$(NODE_SRCS))
 NODE_HDRS := $(wildcard native/libmxnode/*.h)
 
-.PHONY: all kernels gemm-exp node tools clean test-native test-native-tsan test-attention-plan test-attention-doc test-mxfp4-format fake-amdsmi
+.PHONY: all kernels gemm-exp node tools clean test-native test-native-tsan test-attention-plan test-gemm-plan test-attention-doc test-mxfp4-format fake-amdsmi
 all: kernels node tools fake-amdsmi
 
 kernels: $(OUT_LIB)/libmxkernels.so
@@ -141,6 +142,14 @@ test-attention-plan: $(BUILD)/asan/attention_plan_sweep
 	$<
 
 $(BUILD)/asan/attention_plan_sweep: native/kernels/tests/attention_plan_sweep.cc native/kernels/attention_plan.h
+	@mkdir -p $(dir $@)
+	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -Wshadow -fsanitize=address,undefined -fno-sanitize-recover=all \
+	    -fno-omit-frame-pointer -Inative/kernels -o $@ $<
+
+test-gemm-plan: $(BUILD)/asan/gemm_plan_sweep
+	$<
+
+$(BUILD)/asan/gemm_plan_sweep: native/kernels/tests/gemm_plan_sweep.cc native/kernels/gemm_plan.h
 	@mkdir -p $(dir $@)
 	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -Wshadow -fsanitize=address,undefined -fno-sanitize-recover=all \
 	    -fno-omit-frame-pointer -Inative/kernels -o $@ $<

@@ -64,6 +64,10 @@ _SIGNATURES = {
     "mxk_gemm_bf16_ex_ws": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _l,
                                  ctypes.POINTER(ctypes.c_int), _vp]),
     "mxk_gemm_bf16_split_workspace": (_l, []),
+    # the plans of native/kernels/gemm_plan.h (host arithmetic, nothing launched)
+    "mxk_gemm_bf16_ex_plan": (_i, [_i] * 16 + [_l, ctypes.POINTER(ctypes.c_long)]),
+    "mxk_gemm_bf16_tn_plan": (_i, [_i] * 10 + [ctypes.POINTER(ctypes.c_long)]),
+    "mxk_gemm_bf16_dgrad_swiglu_plan": (_i, [_i] * 14 + [ctypes.POINTER(ctypes.c_long)]),
     "mxk_gemm_bf16_dgrad_swiglu": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "mxk_gemm_bf16_w13_swiglu": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "mxk_gemm_bf16_tn_variant": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),

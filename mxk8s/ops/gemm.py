@@ -131,7 +131,8 @@ def split_plan(nwg: int, K: int, cus: int) -> tuple[int, int]:
     """(whole tiles, tail tiles run as K halves) for ``nwg`` 256^2 output
     tiles on ``cus`` CUs: the tail of a last round at most half full is split
     so it occupies the CUs a whole round would, instead of leaving the rest
-    idle.  Mirrors ``mxk_gemm_split_plan`` (gemm_bf16_layouts.hip)."""
+    idle.  Mirrors ``gemm_split_plan`` (gemm_plan.h; exported as
+    ``mxk_gemm_split_plan``)."""
     tail = nwg % cus if nwg > 0 and cus > 0 else 0
     want = tail > 0 and 2 * tail <= cus and K % (2 * XBK) == 0 and K >= 16 * XBK
     return (nwg - tail, tail) if want else (nwg, 0)
@@ -166,7 +167,8 @@ def exclusive() -> bool:
 # ---- staggered rounds (gemm_bf16.hip schedule 54) --------------------------
 def stagger_plan(T: int, K: int, cus: int) -> int:
     """Split tiles per XCD of the staggered-round schedule, 0 when it does not
-    apply.  Mirrors ``mxk_gemm_stagger_plan`` (gemm_bf16.hip)."""
+    apply.  Mirrors ``gemm_stagger_plan`` (gemm_plan.h; exported as
+    ``mxk_gemm_stagger_plan``)."""
     if T <= 0 or T % 8 or cus < 16 or K % (2 * XBK) or K < 4 * XBK:
         return 0
     tx, cx = T // 8, cus // 8

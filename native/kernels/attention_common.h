@@ -6,30 +6,12 @@
 #include "attention_plan.h"
 #include "mx_common.h"
 
-// Runs the statement with NAME a constexpr bool equal to the run-time `flag`,
-// so one launch with NAME among its template arguments stands for
-// `if (flag) launch<true, ..> else launch<false, ..>`.
-#define MXK_WITH_BOOL(NAME, flag, ...) \
-  do {                                 \
-    if (flag) {                        \
-      constexpr bool NAME = true;      \
-      __VA_ARGS__;                     \
-    } else {                           \
-      constexpr bool NAME = false;     \
-      __VA_ARGS__;                     \
-    }                                  \
-  } while (0)
-
 namespace {
 // every pointer a multiple of `n` bytes (null included)
 template <class... P>
 inline bool attn_aligned(unsigned n, P... p) {
   return (reinterpret_cast<uintptr_t>(p) | ...) % n == 0;
 }
-
-// the bf16 view of an entry point's untyped tensor argument
-inline const uint16_t* bf(const void* p) { return static_cast<const uint16_t*>(p); }
-inline uint16_t* bf(void* p) { return static_cast<uint16_t*>(p); }
 
 constexpr int BKV = 64;         // keys per block
 constexpr int NT = 256;         // threads per workgroup

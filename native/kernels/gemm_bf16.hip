@@ -113,10 +113,9 @@
 // loop-exit accumulator copies racing the inline-asm MFMAs; their A/B logs
 // stay in profiles/r1_gemm_*/ (numbered by the old ids: old 34 = 0,
 // 31 = 1, 29 = 2, 30 = 3, 32 = 4, 35 = 5, 36 = 6).
-#include <atomic>
-#include <cstdlib>
 #include <type_traits>
 
+#include "gemm_plan.h"
 #include "gemm_tn_core.h"
 
 // ---------------------------------------------------------------------------
@@ -468,38 +467,24 @@ MXK_API int mxk_gemm_bf16_ex_variant(const void* A, const void* B, void* C, int 
 
 MXK_API int mxk_gemm_available_cus(void);   // gemm_bf16_layouts.hip
 
-// Staggered-round plan (schedule 54, mxk_gemm_bf16_tn_w4j_stag): split tiles
-// per XCD (half the XCD's CUs), or 0 when it does not apply - T % 8, fewer
-// than two whole rounds, or K halves shorter than two K-tiles / not whole
-// K-tiles.  Pure host arithmetic (tests/test_gemm_plan.py).
-MXK_API int mxk_gemm_stagger_plan(long T, int K, int cus) {
-  if (T <= 0 || T % 8 || cus < 16 || K % (2 * BK) || K < 4 * BK) return 0;
-  const long tx = T / 8;
-  const int cx = cus / 8;
-  const int sx = cx / 2;
-  if (sx <= 0 || tx < 2 * cx) return 0;
-  return sx;
-}
+// Staggered-round plan (schedule 54, mxk_gemm_bf16_tn_w4j_stag): gemm_plan.h
+// gemm_stagger_plan, for the host tests (tests/test_gemm_plan.py).
+MXK_API int mxk_gemm_stagger_plan(long T, int K, int cus) { return gemm_stagger_plan(T, K, cus); }
 
-// stagger_part() of workgroup b on the host: out = {virtual tile, part, slot}
+// stagger_part() / stagger_part_xcd() of workgroup b on the host: out =
+// {virtual tile, part, slot}
+static void put_part(const StaggerPart& p, int* out) { out[0] = p.vtile, out[1] = p.part, out[2] = p.slot; }
 MXK_API void mxk_gemm_stagger_part(int b, int T, int sx, int* out) {
-  const StaggerPart p = stagger_part(b, T, sx);
-  out[0] = p.vtile;
-  out[1] = p.part;
-  out[2] = p.slot;
+  put_part(stagger_part(b, T, sx), out);
 }
-
 MXK_API void mxk_gemm_stagger_part_xcd(int b, int T, int cx, int* out) {
-  const StaggerPart p = stagger_part_xcd(b, T, cx);
-  out[0] = p.vtile;
-  out[1] = p.part;
-  out[2] = p.slot;
+  put_part(stagger_part_xcd(b, T, cx), out);
 }
 
 namespace {
 constexpr int kNumVariants = 59;
 constexpr int kDefaultVariant = 52;
-constexpr int kNarrowCVariant = 1;
+constexpr int kNarrowCVariant = GEMM_TN_NARROW_C;
 constexpr const char* kVariantNames[kNumVariants] = {
     "w4i", "w4i_narrow", "w4i_b3_91", "w4i_b3_96", "w4i_r1", "w4ip", "w4j_hb", "w4j_2bar",
     "w4j_hb_st", "x2_hb", "diag_nostore", "w4ip_hb_st", "w4ip_hb_nt", "w4j_earlyb",
@@ -519,53 +504,38 @@ int mxk_gemm_tn_exp_launch(int v, int nwg, hipStream_t stream, const void* A, co
 #endif
 namespace {
 
-template <int EPI>
-void launch_w4j(int nwg, hipStream_t stream, const void* a, const void* b, void* c, int M, int N,
-                int K, int lda, int ldb, int ldc) {
-  MXK_LAUNCH_GEMM((mxk_gemm_bf16_tn_w4j<1, EPI>), dim3(nwg), dim3(W4_THREADS), stream,
-                     static_cast<const uint16_t*>(a), static_cast<const uint16_t*>(b),
-                     static_cast<uint16_t*>(c), M, N, K, lda, ldb, ldc);
-}
-
 void launch_256(int v, int nwg, hipStream_t stream, const void* A, const void* Bt, void* C, int M,
                 int N, int K, int lda, int ldb, int ldc) {
+#define MXK_TN(KERNEL, grid)                                                                  \
+  MXK_LAUNCH_GEMM((KERNEL), dim3(grid), dim3(W4_THREADS), stream, bf(A), bf(Bt), bf(C), M, N, K, lda, \
+                  ldb, ldc)
   switch (v) {
-    case 47:
-      MXK_LAUNCH_GEMM((mxk_gemm_bf16_tn_w4k<1, 4>), dim3(nwg), dim3(W4_THREADS), stream,
-                         static_cast<const uint16_t*>(A), static_cast<const uint16_t*>(Bt),
-                         static_cast<uint16_t*>(C), M, N, K, lda, ldb, ldc);
-      break;
-    case 52:
-      MXK_LAUNCH_GEMM((mxk_gemm_bf16_tn_w4k<1, 4, 0, 1>), dim3(nwg), dim3(W4_THREADS), stream,
-                         static_cast<const uint16_t*>(A), static_cast<const uint16_t*>(Bt),
-                         static_cast<uint16_t*>(C), M, N, K, lda, ldb, ldc);
-      break;
+    case 47: MXK_TN((mxk_gemm_bf16_tn_w4k<1, 4>), nwg); break;
+    case 52: MXK_TN((mxk_gemm_bf16_tn_w4k<1, 4, 0, 1>), nwg); break;
 #ifdef MXK_GEMM_EXPERIMENTS
     case 58: {
       // persistent: one workgroup per available CU (at most one per tile);
       // an A/B record (profiles/r5_gemm/persistent_58_ab.txt: equal to 52
       // within noise at 8192^3 and the step shapes)
       const int cus = mxk_gemm_available_cus();
-      const int grid = cus > 0 && cus < nwg ? cus : nwg;
-      MXK_LAUNCH_GEMM((mxk_gemm_bf16_tn_w4p<1, 1>), dim3(grid), dim3(W4_THREADS), stream,
-                         static_cast<const uint16_t*>(A), static_cast<const uint16_t*>(Bt),
-                         static_cast<uint16_t*>(C), M, N, K, lda, ldb, ldc);
+      MXK_TN((mxk_gemm_bf16_tn_w4p<1, 1>), cus > 0 && cus < nwg ? cus : nwg);
       break;
     }
 #endif
-    case 1: launch_w4j<0>(nwg, stream, A, Bt, C, M, N, K, lda, ldb, ldc); break;
-    case 6: launch_w4j<2>(nwg, stream, A, Bt, C, M, N, K, lda, ldb, ldc); break;
+    case 1: MXK_TN((mxk_gemm_bf16_tn_w4j<1, 0>), nwg); break;
+    case 6: MXK_TN((mxk_gemm_bf16_tn_w4j<1, 2>), nwg); break;
     case 9:
       // the layout kernel (gemm_bf16_layouts.hip) on K-major operands
       mxk_gemm_bf16_ex_variant(A, Bt, C, M, N, K, lda, ldb, ldc, 1, 1, 2, stream);
       break;
-    case 26: launch_w4j<4>(nwg, stream, A, Bt, C, M, N, K, lda, ldb, ldc); break;
+    case 26: MXK_TN((mxk_gemm_bf16_tn_w4j<1, 4>), nwg); break;
     default:
 #ifdef MXK_GEMM_EXPERIMENTS
       mxk_gemm_tn_exp_launch(v, nwg, stream, A, Bt, C, M, N, K, lda, ldb, ldc);
 #endif
       break;
   }
+#undef MXK_TN
 }
 
 // Production builds carry the default (52), its ORDER-0 twin (47), the
@@ -583,26 +553,24 @@ bool variant_built(int v) {
 
 // MXK_TN_VARIANT=v: another built schedule as the default (same-box A/B of
 // the training step; the validator times schedules directly)
-int default_variant() {
-  static const int v = [] {
-    const char* e = std::getenv("MXK_TN_VARIANT");
-    const int x = e ? std::atoi(e) : kDefaultVariant;
-    return variant_built(x) && x != kNarrowCVariant ? x : kDefaultVariant;
-  }();
-  return v;
+int fix_default_variant(int x) {
+  return variant_built(x) && x != kNarrowCVariant ? x : kDefaultVariant;
 }
+mxk::EnvKnob g_default_variant{"MXK_TN_VARIANT", kDefaultVariant, fix_default_variant};
 
-// every schedule but 1 stores 16 B per lane: C 16-B aligned, ldc % 8 == 0
-bool wide_c_ok(const void* C, int ldc) {
-  return (ldc % 8 == 0) && (reinterpret_cast<uintptr_t>(C) % 16 == 0);
+// the K-major (TN) view of an entry point's arguments
+GemmOperands tn_operands(const void* A, const void* Bt, const void* C, int M, int N, int K, int lda,
+                         int ldb, int ldc) {
+  return {M, N, K, lda, ldb, ldc, 1, 1, gemm_addr_bits(A), gemm_addr_bits(Bt), gemm_addr_bits(C)};
 }
 }  // namespace
 
 // Benchmark hook: run schedule `variant` of the 256x256 kernel (fast shapes only).
 MXK_API int mxk_gemm_bf16_tn_variant(const void* A, const void* Bt, void* C, int M, int N, int K,
                                      int lda, int ldb, int ldc, int variant, hipStream_t stream) {
+  // every schedule but the narrow-C one stores 16 B per lane
   if (M % BM || N % BN || K % BK || variant < 0 || variant >= kNumVariants ||
-      (variant != kNarrowCVariant && !wide_c_ok(C, ldc)))
+      (variant != kNarrowCVariant && !gemm_wide_c(tn_operands(A, Bt, C, M, N, K, lda, ldb, ldc))))
     return static_cast<int>(hipErrorInvalidValue);
   if (!variant_built(variant)) return static_cast<int>(hipErrorNotSupported);
   launch_256(variant, (M / BM) * (N / BN), stream, A, Bt, C, M, N, K, lda, ldb, ldc);
@@ -621,75 +589,67 @@ MXK_API int mxk_gemm_bf16_tn_is_ablation(int variant) {
 
 MXK_API int mxk_gemm_bf16_tn(const void* A, const void* Bt, void* C, int M, int N, int K,
                              int lda, int ldb, int ldc, hipStream_t stream) {
-  if (M <= 0 || N <= 0 || K <= 0) return static_cast<int>(hipErrorInvalidValue);
-  const bool fast = (M % BM == 0) && (N % BN == 0) && (K % BK == 0) && (lda % 8 == 0) &&
-                    (ldb % 8 == 0) && (ldc % 4 == 0) &&
-                    (reinterpret_cast<uintptr_t>(A) % 16 == 0) &&
-                    (reinterpret_cast<uintptr_t>(Bt) % 16 == 0) &&
-                    (reinterpret_cast<uintptr_t>(C) % 8 == 0);
-  if (fast) {
-    launch_256(wide_c_ok(C, ldc) ? default_variant() : kNarrowCVariant, (M / BM) * (N / BN), stream,
-               A, Bt, C, M, N, K, lda, ldb, ldc);
-  } else {
-    dim3 grid((N + 63) / 64, (M + 63) / 64);
-    hipLaunchKernelGGL(mxk_gemm_bf16_tn_generic, grid, dim3(256), 0, stream,
-                       static_cast<const uint16_t*>(A), static_cast<const uint16_t*>(Bt),
-                       static_cast<uint16_t*>(C), M, N, K, lda, ldb, ldc);
-  }
+  const GemmTnPlan p =
+      gemm_tn_plan(tn_operands(A, Bt, C, M, N, K, lda, ldb, ldc), g_default_variant.get());
+  if (p.status) return static_cast<int>(hipErrorInvalidValue);
+  if (p.generic)
+    hipLaunchKernelGGL(mxk_gemm_bf16_tn_generic, dim3(p.grid, p.grid_y), dim3(256), 0, stream, bf(A),
+                       bf(Bt), bf(C), M, N, K, lda, ldb, ldc);
+  else
+    launch_256(p.variant, p.grid, stream, A, Bt, C, M, N, K, lda, ldb, ldc);
   MXK_RETURN_LAUNCH_STATUS();
+}
+
+// gemm_tn_plan of a call, for the host tests: out[0..3] = generic kernel,
+// schedule of the 256-tile kernel (-1 for the generic one), grid x, grid y.
+// default_variant: the resolved MXK_TN_VARIANT.  Launches nothing.
+MXK_API int mxk_gemm_bf16_tn_plan(int M, int N, int K, int lda, int ldb, int ldc, int a_bits,
+                                  int b_bits, int c_bits, int default_variant, long* out) {
+  const GemmOperands o{M, N, K, lda, ldb, ldc, 1, 1, static_cast<unsigned>(a_bits),
+                       static_cast<unsigned>(b_bits), static_cast<unsigned>(c_bits)};
+  const GemmTnPlan p = gemm_tn_plan(o, default_variant);
+  if (p.status || !out) return static_cast<int>(hipErrorInvalidValue);
+  const long f[4] = {p.generic, p.variant, p.grid, p.grid_y};
+  for (int i = 0; i < 4; ++i) out[i] = f[i];
+  return 0;
 }
 
 // gu = x . W13^T and h = silu(gu[:, :F]) * gu[:, F:] in one launch (see the
 // kernel).  M % 256, F % 128, K % 64, 16-B aligned operands, ld* % 8.
-namespace {
-std::atomic<int> g_w13_sched{-1};
-int w13_sched() {
-  int v = g_w13_sched.load(std::memory_order_relaxed);
-  if (v < 0) {
-    const char* e = std::getenv("MXK_W13_SCHED");
-    v = e ? std::atoi(e) : 0;
-    g_w13_sched.store(v, std::memory_order_relaxed);
-  }
-  return v;
-}
-}  // namespace
-
 // K loop of the fused up-projection: 0 three-barrier w4j (default), 1 the
 // one-barrier loop of TN schedule 52, 2 = 0 with non-temporal gu stores,
-// 3 the persistent form (experiments library; env MXK_W13_SCHED)
-MXK_API void mxk_gemm_w13_set_sched(int v) { g_w13_sched.store(v >= 1 && v <= 3 ? v : 0); }
+// 3 the persistent form (experiments library).  Raw from MXK_W13_SCHED; the
+// setter clamps.
+namespace {
+mxk::EnvKnob g_w13_sched{"MXK_W13_SCHED", 0, nullptr};
+}  // namespace
+MXK_API void mxk_gemm_w13_set_sched(int v) { g_w13_sched.set(v >= 1 && v <= 3 ? v : 0); }
 
 MXK_API int mxk_gemm_bf16_w13_swiglu(const void* x, const void* w13, void* gu, void* h, int M,
                                      int F, int K, int ldx, int ldw, int ldgu, int ldh,
                                      hipStream_t stream) {
-  auto al = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
-  if (M <= 0 || F <= 0 || K <= 0 || M % BM || F % 128 || K % BK || ldx % 8 || ldw % 8 ||
-      ldgu % 8 || ldh % 8 || !al(x) || !al(w13) || !al(gu) || !al(h) ||
-      static_cast<long>(F + 128) * ldw * 2 >= (1L << 31))
+  // gu [M][2F] is the GEMM's C (F % 128); own: h, and W13's (F + 128)-row panel under 2 GiB
+  const GemmOperands o = tn_operands(x, w13, gu, M, gemm_twice(F), K, ldx, ldw, ldgu);
+  if (M <= 0 || F <= 0 || K <= 0 || !gemm_tiles_ok(o) || !gemm_wide_c(o) || ldh % 8 ||
+      gemm_addr_bits(h) % 16 || (F + 128L) * ldw * 2 >= (1L << 31))
     return static_cast<int>(hipErrorInvalidValue);
   const int nwg = (M / BM) * (F / 128);
+#define MXK_W13(KERNEL, grid)                                                                      \
+  MXK_LAUNCH_GEMM((KERNEL), dim3(grid), dim3(W4_THREADS), stream, bf(x), bf(w13), bf(gu), bf(h), M, F, K, \
+                  ldx, ldw, ldgu, ldh)
 #ifdef MXK_GEMM_EXPERIMENTS
   // A/B records (experiments library): 1 = one-barrier K loop, 2 = non-temporal
   // gu stores; both step-neutral (profiles/r4_step/)
-  if (w13_sched() == 3) {
+  const int sched = g_w13_sched.get();
+  if (sched == 3) {
     const int cus = mxk_gemm_available_cus();
-    const int grid = cus > 0 && cus < nwg ? cus : nwg;
-    MXK_LAUNCH_GEMM(mxk_gemm_bf16_w13_swiglu_p, dim3(grid), dim3(W4_THREADS), stream,
-                    static_cast<const uint16_t*>(x), static_cast<const uint16_t*>(w13),
-                    static_cast<uint16_t*>(gu), static_cast<uint16_t*>(h), M, F, K, ldx, ldw, ldgu, ldh);
-  } else if (w13_sched() == 2)
-    MXK_LAUNCH_GEMM((mxk_gemm_bf16_w13_swiglu_k<false, true>), dim3(nwg), dim3(W4_THREADS), stream,
-                    static_cast<const uint16_t*>(x), static_cast<const uint16_t*>(w13),
-                    static_cast<uint16_t*>(gu), static_cast<uint16_t*>(h), M, F, K, ldx, ldw, ldgu, ldh);
-  else if (w13_sched() == 1)
-    MXK_LAUNCH_GEMM((mxk_gemm_bf16_w13_swiglu_k<true>), dim3(nwg), dim3(W4_THREADS), stream,
-                    static_cast<const uint16_t*>(x), static_cast<const uint16_t*>(w13),
-                    static_cast<uint16_t*>(gu), static_cast<uint16_t*>(h), M, F, K, ldx, ldw, ldgu, ldh);
+    MXK_W13(mxk_gemm_bf16_w13_swiglu_p, cus > 0 && cus < nwg ? cus : nwg);
+  } else if (sched == 2) MXK_W13((mxk_gemm_bf16_w13_swiglu_k<false, true>), nwg);
+  else if (sched == 1) MXK_W13((mxk_gemm_bf16_w13_swiglu_k<true>), nwg);
   else
 #endif
-    MXK_LAUNCH_GEMM((mxk_gemm_bf16_w13_swiglu_k<false>), dim3(nwg), dim3(W4_THREADS), stream,
-                    static_cast<const uint16_t*>(x), static_cast<const uint16_t*>(w13),
-                    static_cast<uint16_t*>(gu), static_cast<uint16_t*>(h), M, F, K, ldx, ldw, ldgu, ldh);
+    MXK_W13((mxk_gemm_bf16_w13_swiglu_k<false>), nwg);
+#undef MXK_W13
   MXK_RETURN_LAUNCH_STATUS();
 }
 
@@ -703,14 +663,13 @@ MXK_API int mxk_gemm_bf16_w13_swiglu(const void* x, const void* w13, void* gu, v
 MXK_API int mxk_gemm_bf16_rope(const void* A, const void* Bt, void* C, int M, int N, int K,
                                int lda, int ldb, int ldc, const float* rcos, const float* rsin,
                                int S, int rope_cols, hipStream_t stream) {
-  auto al = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
-  if (M <= 0 || N <= 0 || K <= 0 || M % BM || N % BN || K % BK || lda % 8 || ldb % 8 ||
-      ldc % 8 || S <= 0 || S % 256 || M % S || rope_cols < 0 || rope_cols % 128 ||
-      rope_cols > N || !al(A) || !al(Bt) || !al(C) || !rcos || !rsin || !al(rcos) || !al(rsin))
+  const GemmOperands o = tn_operands(A, Bt, C, M, N, K, lda, ldb, ldc);
+  if (M <= 0 || N <= 0 || K <= 0 || !gemm_tiles_ok(o) || !gemm_wide_c(o) || S <= 0 || S % 256 ||
+      M % S || rope_cols < 0 || rope_cols % 128 || rope_cols > N || !rcos || !rsin ||
+      gemm_addr_bits(rcos) % 16 || gemm_addr_bits(rsin) % 16)
     return static_cast<int>(hipErrorInvalidValue);
   MXK_LAUNCH_GEMM((mxk_gemm_bf16_tn_w4k<1, 5, 0, 1>), dim3((M / BM) * (N / BN)), dim3(W4_THREADS),
-                  stream, static_cast<const uint16_t*>(A), static_cast<const uint16_t*>(Bt),
-                  static_cast<uint16_t*>(C), M, N, K, lda, ldb, ldc, rcos, rsin, S, rope_cols);
+                  stream, bf(A), bf(Bt), bf(C), M, N, K, lda, ldb, ldc, rcos, rsin, S, rope_cols);
   MXK_RETURN_LAUNCH_STATUS();
 }
 

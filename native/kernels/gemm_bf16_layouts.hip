@@ -26,12 +26,9 @@
 #include <mutex>
 #include <map>
 #include <algorithm>
-#include <atomic>
-#include <cstdlib>
 
+#include "gemm_plan.h"
 #include "mx_common.h"
-
-#include <cstdlib>
 
 namespace {
 constexpr int XT = 256;          // threads (4 waves)
@@ -838,165 +835,150 @@ mxk_gemm_split_fixup(const float* __restrict__ ws, uint16_t* __restrict__ C, int
   *reinterpret_cast<uint2*>(cp + 4) = hi;
 }
 
+// ---------------------------------------------------------------------------
+// Host side.  gemm_plan.h decides what a call runs; the entry points below
+// read the knobs, ask it and carry the plan out.
+// ---------------------------------------------------------------------------
 namespace {
-std::atomic<int> g_x2_order{-1};
-int x2_order() {
-#ifndef MXK_GEMM_EXPERIMENTS
-  return 0;   // the B-outer order is built into the experiments library only
-#endif
-  int v = g_x2_order.load(std::memory_order_relaxed);
-  if (v < 0) {
-    const char* e = std::getenv("MXK_X2_ORDER");
-    v = e && std::atoi(e) == 1 ? 1 : 0;
-    g_x2_order.store(v, std::memory_order_relaxed);
-  }
-  return v;
-}
+// MFMA order of the layout kernel's K-tile: 0 A-fragment outer (default), 1
+// B-fragment outer.  The B-outer instances are built into the experiments
+// library only; gemm_plan.h ignores the knob elsewhere.
+int fix_x2_order(int v) { return v == 1 ? 1 : 0; }
+mxk::EnvKnob g_x2_order{"MXK_X2_ORDER", 0, fix_x2_order};
+// dgrad-SwiGLU epilogue mode, raw (gemm_plan.h gemm_dgrad_swiglu_plan)
+mxk::EnvKnob g_swiglu_epi{"MXK_SWIGLU_WIDE", 4, nullptr};
+
+int hw_cus();
+int device_cus();
 }  // namespace
 
-// MFMA order of the layout kernel's K-tile: 0 A-fragment outer (default), 1
-// B-fragment outer (env MXK_X2_ORDER)
-MXK_API void mxk_gemm_x2_set_order(int v) { g_x2_order.store(v == 1 ? 1 : 0); }
-
-template <bool AN, bool BN>
-static void launch_x(int sched, bool wide, int nwg, hipStream_t stream, const uint16_t* a,
-                     const uint16_t* b, uint16_t* c, int M, int N, int K, int lda, int ldb,
-                     int ldc) {
-  // sched: -1 = the one-barrier x kernel, 0 = x2, 1 = x2 at hipBLASLt positions;
-  // x2_order() adds bit 1 (B-outer MFMA order, MXK_X2_ORDER=1)
-  if (sched < 0) {
-    MXK_LAUNCH_GEMM((mxk_gemm_bf16_x_kernel<AN, BN>), dim3(nwg), dim3(XT), stream, a, b, c,
-                    M, N, K, lda, ldb, ldc);
-    return;
-  }
-  switch ((sched | (x2_order() ? 2 : 0)) * 2 + (wide ? 1 : 0)) {
-#define MXK_X2_CASE(S, W)                                                                        \
-  case S * 2 + W:                                                                                \
-    MXK_LAUNCH_GEMM((mxk_gemm_bf16_x2_kernel<AN, BN, W, S>), dim3(nwg), dim3(XT), stream, a, b, c, \
-                    M, N, K, lda, ldb, ldc);                                                     \
-    break;
-    MXK_X2_CASE(0, 0) MXK_X2_CASE(0, 1) MXK_X2_CASE(1, 0) MXK_X2_CASE(1, 1)
-#ifdef MXK_GEMM_EXPERIMENTS
-    // B-outer order: step-neutral (profiles/r4_step/step_ab_set2.txt), A/B only
-    MXK_X2_CASE(2, 0) MXK_X2_CASE(2, 1) MXK_X2_CASE(3, 0) MXK_X2_CASE(3, 1)
-#endif
-#undef MXK_X2_CASE
-    default: break;
-  }
-}
+MXK_API void mxk_gemm_x2_set_order(int v) { g_x2_order.set(v); }
+MXK_API void mxk_gemm_swiglu_set_epi(int v) { g_swiglu_epi.set(v); }
 
 // 1 if layout-kernel variant v is in this build (4, x2t: experiments only)
-MXK_API int mxk_gemm_bf16_ex_variant_built(int v) {
-#ifdef MXK_GEMM_EXPERIMENTS
-  return v >= 0 && v <= 4;
-#else
-  return v >= 0 && v <= 3;
-#endif
+MXK_API int mxk_gemm_bf16_ex_variant_built(int v) { return v >= 0 && v <= (kMxkExperiments ? 4 : 3); }
+
+// gemm_split_plan (gemm_plan.h) for the host tests (tests/test_gemm_plan.py)
+MXK_API int mxk_gemm_split_plan(long nwg, int K, int cus, long* q_full) {
+  return gemm_split_plan(nwg, K, cus, q_full);
 }
+
+// Bytes of fp32 workspace the split tail of an (M, N) output needs at most
+// (half a round of tiles, two partial tiles each).
+MXK_API long mxk_gemm_bf16_split_workspace(void) { return gemm_split_workspace(hw_cus()); }
 
 MXK_API int mxk_gemm_bf16_tn(const void* A, const void* Bt, void* C, int M, int N, int K,
                              int lda, int ldb, int ldc, hipStream_t stream);
 
 namespace {
-int device_cus();
+// Carries out a GemmExPlan of a layout-kernel family: the whole-tile launch,
+// then under a split the K halves of the tail tiles and the fixup.  The tile
+// map is over all tiles, not the grid, so the whole-tile launch of a split
+// covers tiles [0, q_full).
+template <bool AN, bool BN>
+void launch_ex(const GemmExPlan& p, hipStream_t stream, const uint16_t* a, const uint16_t* b,
+               uint16_t* c, int M, int N, int K, int lda, int ldb, int ldc, float* ws) {
+#define MXK_EX(KERNEL, grid, ...) \
+  MXK_LAUNCH_GEMM((KERNEL), dim3(grid), dim3(XT), stream, a, b, c, M, N, K, lda, ldb, __VA_ARGS__)
+  if (p.family == GEMM_X2T) {
+#ifdef MXK_GEMM_EXPERIMENTS
+    // an A/B record (mixed against x2 on the Llama-3-8B step shapes,
+    // profiles/r3_pass1/layouts_ab.log)
+    MXK_WITH_BOOL(HB, p.hb, MXK_EX((mxk_gemm_bf16_x2t_kernel<AN, BN, HB>), p.grid, ldc));
+#endif
+    return;
+  }
+  if (p.grid > 0 && p.family == GEMM_X) MXK_EX((mxk_gemm_bf16_x_kernel<AN, BN>), p.grid, ldc);
+  else if (p.grid > 0)
+    switch ((p.hb | 2 * p.order) * 2 + p.wide) {
+#define MXK_X2_CASE(S, W) \
+  case S * 2 + W: MXK_EX((mxk_gemm_bf16_x2_kernel<AN, BN, W, S>), p.grid, ldc); break;
+      MXK_X2_CASE(0, 0) MXK_X2_CASE(0, 1) MXK_X2_CASE(1, 0) MXK_X2_CASE(1, 1)
+#ifdef MXK_GEMM_EXPERIMENTS
+      // B-outer order: step-neutral (profiles/r4_step/step_ab_set2.txt), A/B only
+      MXK_X2_CASE(2, 0) MXK_X2_CASE(2, 1) MXK_X2_CASE(3, 0) MXK_X2_CASE(3, 1)
+#endif
+#undef MXK_X2_CASE
+      default: break;
+    }
+  if (!p.split) return;
+  MXK_WITH_BOOL(HB, p.hb,
+                MXK_EX((mxk_gemm_bf16_x2_kernel<AN, BN, 0, HB, true>), 2 * p.tail, ldc, nullptr, ws,
+                       p.q_full));
+  hipLaunchKernelGGL(mxk_gemm_split_fixup, dim3(XBM * XBM / (256 * 8), p.tail), dim3(256), 0, stream,
+                     ws, c, M, N, ldc, p.q_full);
+#undef MXK_EX
 }
 
-// x2t: persistent trickle-store layout kernel, one workgroup per CU at most
-template <bool AN, bool BN>
-static void launch_xt(int sched, int nwg, hipStream_t stream, const uint16_t* a, const uint16_t* b,
-                      uint16_t* c, int M, int N, int K, int lda, int ldb, int ldc) {
-  const int cus = device_cus();
-  const int grid = nwg < cus ? nwg : cus;
-  if (sched == 1)
-    MXK_LAUNCH_GEMM((mxk_gemm_bf16_x2t_kernel<AN, BN, 1>), dim3(grid), dim3(XT), stream, a, b,
-                       c, M, N, K, lda, ldb, ldc);
-  else
-    MXK_LAUNCH_GEMM((mxk_gemm_bf16_x2t_kernel<AN, BN, 0>), dim3(grid), dim3(XT), stream, a, b,
-                       c, M, N, K, lda, ldb, ldc);
+// The three mxk_gemm_bf16_ex* entry points: resolve once (gemm_plan.h
+// gemm_ex_plan says which call runs what), then hand off or launch.
+int run_ex(const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc,
+           int a_kmajor, int b_kmajor, int variant, void* ws, long ws_bytes, int* split,
+           hipStream_t stream) {
+  if (split) *split = 0;
+  const GemmOperands o{M, N, K, lda, ldb, ldc, a_kmajor, b_kmajor,
+                       gemm_addr_bits(A), gemm_addr_bits(B), gemm_addr_bits(C)};
+  const GemmExPlan p = gemm_ex_plan(o, variant, device_cus(), g_x2_order.get(), kMxkExperiments,
+                                    gemm_addr_bits(ws), ws ? ws_bytes : 0);
+  if (p.status) return static_cast<int>(hipErrorInvalidValue);
+  if (p.family == GEMM_TN) return mxk_gemm_bf16_tn(A, B, C, M, N, K, lda, ldb, ldc, stream);
+  MXK_WITH_BOOL(AK, a_kmajor,
+                MXK_WITH_BOOL(BK, b_kmajor,
+                              (launch_ex<!AK, !BK>(p, stream, bf(A), bf(B), bf(C), M, N, K, lda, ldb,
+                                                   ldc, static_cast<float*>(ws)))));
+  if (split) *split = p.split;
+  MXK_RETURN_LAUNCH_STATUS();
 }
+}  // namespace
 
 // a_kmajor: A stored [M][K] (1) or [K][M] (0); b_kmajor: B stored [N][K] (1)
 // or [K][N] (0).  Row strides lda/ldb/ldc in elements.  Tiles exactly:
 // M % 256, N % 256, K % 64; returns hipErrorInvalidValue otherwise (callers
-// keep the library GEMM for other shapes).  variant:
-//   1 (default) both K-major -> the validator's TN kernel (gemm_bf16.hip);
-//     both N/M-major (weight gradients) -> x2 at hipBLASLt's positions
-//     (+2-10 % on the Llama-3-8B wgrad shapes); mixed (dgrad) -> x2
-//   2 x2 at hipBLASLt's positions, 3 x2, 0 the one-barrier x kernel
-//   (2, 3 and 0 run every layout on the layout kernel, for A/B)
-//   4 x2t (persistent, trickled C stores; variant 1's schedule per layout,
-//     hipBLASLt positions for TN; x2 when K < 18 * 64)
+// keep the library GEMM for other shapes).  gemm_plan.h lists the variants.
 MXK_API int mxk_gemm_bf16_ex_variant(const void* A, const void* B, void* C, int M, int N, int K,
                                      int lda, int ldb, int ldc, int a_kmajor, int b_kmajor,
                                      int variant, hipStream_t stream) {
-  const auto bytes = [](long rows, long ld) { return rows * ld * 2; };
-  const bool ok = M > 0 && N > 0 && K > 0 && M % XBM == 0 && N % XBM == 0 && K % XBK == 0 &&
-                  lda % 8 == 0 && ldb % 8 == 0 && ldc % 4 == 0 &&
-                  (a_kmajor ? lda >= K : lda >= M) && (b_kmajor ? ldb >= K : ldb >= N) &&
-                  ldc >= N && (a_kmajor || bytes(K, lda) < (1L << 32)) &&
-                  (b_kmajor || bytes(K, ldb) < (1L << 32)) &&
-                  reinterpret_cast<uintptr_t>(A) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(B) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(C) % 8 == 0 && variant >= 0 && variant <= 4;
-  if (!ok) return static_cast<int>(hipErrorInvalidValue);
-  if (variant == 1 && a_kmajor && b_kmajor)
-    return mxk_gemm_bf16_tn(A, B, C, M, N, K, lda, ldb, ldc, stream);
-#ifdef MXK_GEMM_EXPERIMENTS
-  // x2t, the persistent trickle-store kernel: an A/B record (mixed against
-  // x2 on the Llama-3-8B step shapes, profiles/r3_pass1/layouts_ab.log)
-  if (variant == 4 && K >= 18 * XBK && (ldc % 8 == 0) && reinterpret_cast<uintptr_t>(C) % 16 == 0) {
-    const int xs = (a_kmajor == b_kmajor) ? 1 : 0;
-    const int xn = (M / XBM) * (N / XBM);
-    auto a = static_cast<const uint16_t*>(A);
-    auto b = static_cast<const uint16_t*>(B);
-    auto c = static_cast<uint16_t*>(C);
-    if (a_kmajor && b_kmajor)
-      launch_xt<false, false>(xs, xn, stream, a, b, c, M, N, K, lda, ldb, ldc);
-    else if (a_kmajor)
-      launch_xt<false, true>(xs, xn, stream, a, b, c, M, N, K, lda, ldb, ldc);
-    else if (b_kmajor)
-      launch_xt<true, false>(xs, xn, stream, a, b, c, M, N, K, lda, ldb, ldc);
-    else
-      launch_xt<true, true>(xs, xn, stream, a, b, c, M, N, K, lda, ldb, ldc);
-    MXK_RETURN_LAUNCH_STATUS();
-  }
-#endif
-  if (variant == 4) variant = 1;
-  if (variant == 1 && a_kmajor && b_kmajor)
-    return mxk_gemm_bf16_tn(A, B, C, M, N, K, lda, ldb, ldc, stream);
-  const int sched = variant == 0 ? -1 : variant == 2 ? 1 : variant == 3 ? 0
-                  : (!a_kmajor && !b_kmajor) ? 1 : 0;
-  const int nwg = (M / XBM) * (N / XBM);
-  const bool wide = (ldc % 8 == 0) && (reinterpret_cast<uintptr_t>(C) % 16 == 0);
-  auto a = static_cast<const uint16_t*>(A);
-  auto b = static_cast<const uint16_t*>(B);
-  auto c = static_cast<uint16_t*>(C);
-  if (a_kmajor && b_kmajor)
-    launch_x<false, false>(sched, wide, nwg, stream, a, b, c, M, N, K, lda, ldb, ldc);
-  else if (a_kmajor)
-    launch_x<false, true>(sched, wide, nwg, stream, a, b, c, M, N, K, lda, ldb, ldc);
-  else if (b_kmajor)
-    launch_x<true, false>(sched, wide, nwg, stream, a, b, c, M, N, K, lda, ldb, ldc);
-  else
-    launch_x<true, true>(sched, wide, nwg, stream, a, b, c, M, N, K, lda, ldb, ldc);
-  MXK_RETURN_LAUNCH_STATUS();
+  return run_ex(A, B, C, M, N, K, lda, ldb, ldc, a_kmajor, b_kmajor, variant, nullptr, 0, nullptr,
+                stream);
 }
 
-namespace {
-std::atomic<int> g_swiglu_epi{-1};
-int swiglu_epi() {
-  int v = g_swiglu_epi.load(std::memory_order_relaxed);
-  if (v < 0) {
-    const char* e = std::getenv("MXK_SWIGLU_WIDE");
-    v = e ? std::atoi(e) : 4;
-    g_swiglu_epi.store(v, std::memory_order_relaxed);
-  }
-  return v;
+MXK_API int mxk_gemm_bf16_ex(const void* A, const void* B, void* C, int M, int N, int K, int lda,
+                             int ldb, int ldc, int a_kmajor, int b_kmajor, hipStream_t stream) {
+  return run_ex(A, B, C, M, N, K, lda, ldb, ldc, a_kmajor, b_kmajor, 1, nullptr, 0, nullptr, stream);
 }
-}  // namespace
 
-// dgrad-SwiGLU epilogue mode (MXK_SWIGLU_WIDE; see mxk_gemm_bf16_dgrad_swiglu)
-MXK_API void mxk_gemm_swiglu_set_epi(int v) { g_swiglu_epi.store(v); }
+// mxk_gemm_bf16_ex (variant 1) with the split tail: when the output's 256^2
+// tiles fill q whole rounds of the CUs plus a last round at most half full
+// (e.g. 384 tiles on 256 CUs), the tail tiles run as K halves on twice as
+// many workgroups (fp32 partials in ws, summed by a fixup kernel) instead of
+// leaving half the chip idle for a whole round.  Every operand layout; on
+// both-K-major operands the whole tiles of a split then run on x2, not on the
+// TN kernel.  Every other case runs mxk_gemm_bf16_ex unchanged.  `ws` holds
+// >= ws_bytes (mxk_gemm_bf16_split_workspace()); sets *split to 1 when the
+// split path ran.
+MXK_API int mxk_gemm_bf16_ex_ws(const void* A, const void* B, void* C, int M, int N, int K, int lda,
+                                int ldb, int ldc, int a_kmajor, int b_kmajor, void* ws,
+                                long ws_bytes, int* split, hipStream_t stream) {
+  return run_ex(A, B, C, M, N, K, lda, ldb, ldc, a_kmajor, b_kmajor, 1, ws, ws_bytes, split, stream);
+}
+
+// gemm_ex_plan of a call, for the host tests: out[0..8] = GemmFamily, schedule
+// bit, order bit, wide C, grid, tail, q_full, workspace bytes, split flag.
+// Every input explicit (knobs, CU count, build); host arithmetic only,
+// launches nothing.
+MXK_API int mxk_gemm_bf16_ex_plan(int M, int N, int K, int lda, int ldb, int ldc, int a_kmajor,
+                                  int b_kmajor, int a_bits, int b_bits, int c_bits, int variant,
+                                  int cus, int x2_order, int experiments_built, int ws_bits,
+                                  long ws_bytes, long* out) {
+  const GemmOperands o{M, N, K, lda, ldb, ldc, a_kmajor, b_kmajor, static_cast<unsigned>(a_bits),
+                       static_cast<unsigned>(b_bits), static_cast<unsigned>(c_bits)};
+  const GemmExPlan p = gemm_ex_plan(o, variant, cus, x2_order, experiments_built != 0,
+                                    static_cast<unsigned>(ws_bits), ws_bytes);
+  if (p.status || !out) return static_cast<int>(hipErrorInvalidValue);
+  const long f[9] = {p.family, p.hb, p.order, p.wide, p.grid, p.tail, p.q_full, p.ws_bytes, p.split};
+  for (int i = 0; i < 9; ++i) out[i] = f[i];
+  return 0;
+}
 
 #ifdef MXK_GEMM_EXPERIMENTS
 namespace {
@@ -1040,94 +1022,87 @@ const SwigluStagWs* swiglu_stag_ws(hipStream_t stream, int slots) {
 }  // namespace
 #endif
 
+namespace {
+template <int EPI, int SCHED = 0, bool STAG = false>
+void launch_dgrad_swiglu(int grid, hipStream_t stream, const void* dy, const void* w2, const void* gu,
+                         void* dgu, int M, int F, int K, int ld_dy, int ld_w2, float* ws = nullptr,
+                         int* flags = nullptr, int cx = 0) {
+  MXK_LAUNCH_GEMM((mxk_gemm_bf16_x2_kernel<false, true, EPI, SCHED, false, STAG>), dim3(grid),
+                  dim3(XT), stream, bf(dy), bf(w2), bf(dgu), M, F, K, ld_dy, ld_w2, 2 * F, bf(gu), ws,
+                  0, flags, cx);
+}
+}  // namespace
+
 // Down-projection input gradient with the SwiGLU backward fused into the
 // epilogue: d(act) = dy W2 (dy [M][K] K-major, W2 [K][F] F-major) never
 // reaches memory; dgu [M][2F] = d[g | u] is written from gu [M][2F].
 // Tiles exactly (M % 256, F % 256, K % 64); hipErrorInvalidValue otherwise.
+// gemm_plan.h gemm_dgrad_swiglu_plan lists the epilogues (MXK_SWIGLU_WIDE).
 MXK_API int mxk_gemm_bf16_dgrad_swiglu(const void* dy, const void* w2, const void* gu, void* dgu,
                                        int M, int F, int K, int ld_dy, int ld_w2,
                                        hipStream_t stream) {
-  const bool ok = M > 0 && F > 0 && K > 0 && M % XBM == 0 && F % XBM == 0 && K % XBK == 0 &&
-                  ld_dy % 8 == 0 && ld_w2 % 8 == 0 && ld_dy >= K && ld_w2 >= F &&
-                  static_cast<long>(K) * ld_w2 * 2 < (1L << 32) &&
-                  reinterpret_cast<uintptr_t>(dy) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(w2) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(gu) % 8 == 0 &&
-                  reinterpret_cast<uintptr_t>(dgu) % 8 == 0;
-  if (!ok) return static_cast<int>(hipErrorInvalidValue);
-  const int nwg = (M / XBM) * (F / XBM);
-  // 16-B g/u accesses: EPI 4 (LDS-staged, whole lines, pass 0's g/u
-  // prefetched during the last K-tiles) by default, EPI 5 (the same without
-  // the prefetch) with MXK_SWIGLU_WIDE=5, EPI 3 (permlane pairs) with =3, the
-  // 8-B form with =0 (A/B); 6 = EPI 4 without the SwiGLU math (timing only);
-  // 8 = EPI 4 staggered by XCD group (STAG)
-  const int wide_mode = swiglu_epi();
-  const bool wide = wide_mode != 0 && reinterpret_cast<uintptr_t>(gu) % 16 == 0 &&
-                    reinterpret_cast<uintptr_t>(dgu) % 16 == 0 && K >= 2 * XBK;
+  const GemmOperands o{M, F, K, ld_dy, ld_w2, gemm_twice(F), 1, 0,
+                       gemm_addr_bits(dy), gemm_addr_bits(w2), gemm_addr_bits(dgu)};
+  const auto plan = [&](bool stag_ws_ok) {
+    return gemm_dgrad_swiglu_plan(o, gemm_addr_bits(gu), g_swiglu_epi.get(), g_x2_order.get(),
+                                  kMxkExperiments, device_cus(), stag_ws_ok);
+  };
+  GemmDgradSwigluPlan p = plan(true);
+  if (p.status) return static_cast<int>(hipErrorInvalidValue);
+#define MXK_DGRAD_ARGS p.grid, stream, dy, w2, gu, dgu, M, F, K, ld_dy, ld_w2
 #ifdef MXK_GEMM_EXPERIMENTS
-  // A/B records (experiments library): 8 = staggered by XCD group (+0.8 %,
-  // profiles/r4_step/swiglu_epilogue_stagger.log), 6 = no SwiGLU math (timing
-  // ablation), 5 = no g/u prefetch, and the B-outer MFMA order
-  if (wide && wide_mode == 8) {
-    const int cx = device_cus() / 8;
-    const long T = nwg;
-    const bool fits = T % 8 == 0 && cx > 0 && T / 8 >= 2 * cx && K % (2 * XBK) == 0;
-    const SwigluStagWs* w = fits ? swiglu_stag_ws(stream, 4 * cx) : nullptr;
+  // A/B records (experiments library): staggered by XCD group (+0.8 %,
+  // profiles/r4_step/swiglu_epilogue_stagger.log), no SwiGLU math (timing
+  // ablation), no g/u prefetch, and the B-outer MFMA order
+  if (p.stag) {
+    // allocated (outside a capture) only for a call planned staggered; without it, as mode 4
+    const SwigluStagWs* w = swiglu_stag_ws(stream, 4 * p.cx);
     if (w) {
-      MXK_LAUNCH_GEMM((mxk_gemm_bf16_x2_kernel<false, true, 4, 0, false, true>), dim3(nwg + 8 * cx),
-                      dim3(XT), stream, static_cast<const uint16_t*>(dy),
-                      static_cast<const uint16_t*>(w2), static_cast<uint16_t*>(dgu), M, F, K, ld_dy,
-                      ld_w2, 2 * F, static_cast<const uint16_t*>(gu), w->ws, 0, w->flags, cx);
+      launch_dgrad_swiglu<4, 0, true>(MXK_DGRAD_ARGS, w->ws, w->flags, p.cx);
       MXK_RETURN_LAUNCH_STATUS();
     }
+    p = plan(false);
   }
-  if (wide && (wide_mode == 6 || wide_mode == 5 || x2_order())) {
-    if (wide_mode == 6)
-      MXK_LAUNCH_GEMM((mxk_gemm_bf16_x2_kernel<false, true, 6, 0>), dim3(nwg), dim3(XT), stream,
-                      static_cast<const uint16_t*>(dy), static_cast<const uint16_t*>(w2),
-                      static_cast<uint16_t*>(dgu), M, F, K, ld_dy, ld_w2, 2 * F,
-                      static_cast<const uint16_t*>(gu));
-    else if (wide_mode == 5)
-      MXK_LAUNCH_GEMM((mxk_gemm_bf16_x2_kernel<false, true, 5, 0>), dim3(nwg), dim3(XT), stream,
-                      static_cast<const uint16_t*>(dy), static_cast<const uint16_t*>(w2),
-                      static_cast<uint16_t*>(dgu), M, F, K, ld_dy, ld_w2, 2 * F,
-                      static_cast<const uint16_t*>(gu));
-    else
-      MXK_LAUNCH_GEMM((mxk_gemm_bf16_x2_kernel<false, true, 4, 2>), dim3(nwg), dim3(XT), stream,
-                      static_cast<const uint16_t*>(dy), static_cast<const uint16_t*>(w2),
-                      static_cast<uint16_t*>(dgu), M, F, K, ld_dy, ld_w2, 2 * F,
-                      static_cast<const uint16_t*>(gu));
-    MXK_RETURN_LAUNCH_STATUS();
-  }
-#endif
-  if (wide && wide_mode == 3)
-    MXK_LAUNCH_GEMM((mxk_gemm_bf16_x2_kernel<false, true, 3, 0>), dim3(nwg), dim3(XT), stream,
-                       static_cast<const uint16_t*>(dy), static_cast<const uint16_t*>(w2),
-                       static_cast<uint16_t*>(dgu), M, F, K, ld_dy, ld_w2, 2 * F,
-                       static_cast<const uint16_t*>(gu));
-  else if (wide)
-    MXK_LAUNCH_GEMM((mxk_gemm_bf16_x2_kernel<false, true, 4, 0>), dim3(nwg), dim3(XT), stream,
-                       static_cast<const uint16_t*>(dy), static_cast<const uint16_t*>(w2),
-                       static_cast<uint16_t*>(dgu), M, F, K, ld_dy, ld_w2, 2 * F,
-                       static_cast<const uint16_t*>(gu));
+  if (p.epi == 6) launch_dgrad_swiglu<6>(MXK_DGRAD_ARGS);
+  else if (p.epi == 5) launch_dgrad_swiglu<5>(MXK_DGRAD_ARGS);
+  else if (p.order) launch_dgrad_swiglu<4, 2>(MXK_DGRAD_ARGS);
   else
-    MXK_LAUNCH_GEMM((mxk_gemm_bf16_x2_kernel<false, true, 2, 0>), dim3(nwg), dim3(XT), stream,
-                       static_cast<const uint16_t*>(dy), static_cast<const uint16_t*>(w2),
-                       static_cast<uint16_t*>(dgu), M, F, K, ld_dy, ld_w2, 2 * F,
-                       static_cast<const uint16_t*>(gu));
+#endif
+  if (p.epi == 3) launch_dgrad_swiglu<3>(MXK_DGRAD_ARGS);
+  else if (p.epi == 4) launch_dgrad_swiglu<4>(MXK_DGRAD_ARGS);
+  else launch_dgrad_swiglu<2>(MXK_DGRAD_ARGS);
+#undef MXK_DGRAD_ARGS
   MXK_RETURN_LAUNCH_STATUS();
 }
 
+// gemm_dgrad_swiglu_plan of a call, for the host tests: out[0..4] = EPI, order
+// bit, STAG, grid, cx.  Every input explicit; launches nothing.
+MXK_API int mxk_gemm_bf16_dgrad_swiglu_plan(int M, int F, int K, int ld_dy, int ld_w2, int dy_bits,
+                                            int w2_bits, int gu_bits, int dgu_bits, int mode,
+                                            int x2_order, int experiments_built, int cus,
+                                            int stag_ws_ok, long* out) {
+  const GemmOperands o{M, F, K, ld_dy, ld_w2, gemm_twice(F), 1, 0, static_cast<unsigned>(dy_bits),
+                       static_cast<unsigned>(w2_bits), static_cast<unsigned>(dgu_bits)};
+  const GemmDgradSwigluPlan p =
+      gemm_dgrad_swiglu_plan(o, static_cast<unsigned>(gu_bits), mode, x2_order,
+                             experiments_built != 0, cus, stag_ws_ok != 0);
+  if (p.status || !out) return static_cast<int>(hipErrorInvalidValue);
+  const long f[5] = {p.epi, p.order, p.stag, p.grid, p.cx};
+  for (int i = 0; i < 5; ++i) out[i] = f[i];
+  return 0;
+}
+
 // ---- compute units the GEMMs may plan for -------------------------------
-// Every round / split-tail decision below assumes `cus` workgroups run at
-// once.  With collectives in flight (the ZeRO-1 reduce-scatter under the
-// backward, the parameter all-gather under the forward) RCCL's kernels hold
-// some CUs for the whole collective, and a GEMM whose tiles exactly fill the
-// chip then runs one extra, nearly empty round.  mxk_gemm_set_reserved_cus(k)
-// (or MXK_GEMM_RESERVED_CUS=k) tells the planner that k CUs are taken: rounds
-// and the split tail are sized for the CUs that are left.
+// Every round / split-tail decision assumes `cus` workgroups run at once.
+// With collectives in flight (the ZeRO-1 reduce-scatter under the backward,
+// the parameter all-gather under the forward) RCCL's kernels hold some CUs
+// for the whole collective, and a GEMM whose tiles exactly fill the chip then
+// runs one extra, nearly empty round.  mxk_gemm_set_reserved_cus(k) (or
+// MXK_GEMM_RESERVED_CUS=k) tells the planner that k CUs are taken: rounds and
+// the split tail are sized for the CUs that are left.
 namespace {
-std::atomic<int> g_reserved_cus{-1};
+int fix_reserved_cus(int v) { return std::max(0, v); }
+mxk::EnvKnob g_reserved_cus{"MXK_GEMM_RESERVED_CUS", 0, fix_reserved_cus};
 
 int hw_cus() {
   static thread_local int dev_cached = -1, cus = 256;
@@ -1141,34 +1116,16 @@ int hw_cus() {
   return cus;
 }
 
-int reserved_cus() {
-  int r = g_reserved_cus.load(std::memory_order_relaxed);
-  if (r < 0) {
-    const char* e = std::getenv("MXK_GEMM_RESERVED_CUS");
-    r = e ? std::max(0, std::atoi(e)) : 0;
-    g_reserved_cus.store(r, std::memory_order_relaxed);
-  }
-  return r;
-}
+int device_cus() { return std::max(1, hw_cus() - g_reserved_cus.get()); }
 
-int device_cus() { return std::max(1, hw_cus() - reserved_cus()); }
-
-std::atomic<int> g_exclusive{-1};
-int exclusive() {
-  int e = g_exclusive.load(std::memory_order_relaxed);
-  if (e < 0) {
-    const char* v = std::getenv("MXK_GEMM_EXCLUSIVE");
-    e = v && std::atoi(v) ? 1 : 0;
-    g_exclusive.store(e, std::memory_order_relaxed);
-  }
-  return e;
-}
+int fix_exclusive(int v) { return v ? 1 : 0; }
+mxk::EnvKnob g_exclusive{"MXK_GEMM_EXCLUSIVE", 0, fix_exclusive};
 std::mutex g_excl_mu;
 std::map<std::pair<int, const void*>, size_t> g_excl;
 }  // namespace
 
 size_t mxk_excl_lds(const void* kernel) {
-  if (!exclusive()) return 0;
+  if (!g_exclusive.get()) return 0;
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return 0;
   std::lock_guard<std::mutex> lk(g_excl_mu);
@@ -1185,100 +1142,8 @@ size_t mxk_excl_lds(const void* kernel) {
   return add;
 }
 
-MXK_API void mxk_gemm_set_exclusive(int on) { g_exclusive.store(on ? 1 : 0); }
-MXK_API int mxk_gemm_exclusive(void) { return exclusive(); }
-
-MXK_API void mxk_gemm_set_reserved_cus(int n) { g_reserved_cus.store(std::max(0, n)); }
-MXK_API int mxk_gemm_reserved_cus(void) { return reserved_cus(); }
+MXK_API void mxk_gemm_set_exclusive(int on) { g_exclusive.set(on); }
+MXK_API int mxk_gemm_exclusive(void) { return g_exclusive.get(); }
+MXK_API void mxk_gemm_set_reserved_cus(int n) { g_reserved_cus.set(n); }
+MXK_API int mxk_gemm_reserved_cus(void) { return g_reserved_cus.get(); }
 MXK_API int mxk_gemm_available_cus(void) { return device_cus(); }
-
-// The split-tail plan for nwg 256^2 output tiles over `cus` CUs and depth K
-// (pure host arithmetic; tests/test_gemm_plan.py checks it on the CPU):
-// returns the number of tail tiles run as K halves (0: no split) and sets
-// *q_full to the tiles that run whole.
-MXK_API int mxk_gemm_split_plan(long nwg, int K, int cus, long* q_full) {
-  const int tail = nwg > 0 && cus > 0 ? static_cast<int>(nwg % cus) : 0;
-  const bool want = tail > 0 && 2 * tail <= cus && K % (2 * XBK) == 0 && K >= 16 * XBK;
-  if (q_full) *q_full = want ? nwg - tail : nwg;
-  return want ? tail : 0;
-}
-
-namespace {
-
-template <bool AN, bool BN>
-void launch_split(int sched, bool wide, int nwg, int q_full, hipStream_t stream, const uint16_t* a,
-                  const uint16_t* b, uint16_t* c, int M, int N, int K, int lda, int ldb, int ldc,
-                  float* ws) {
-  // whole tiles [0, q_full) (the tile map is over all nwg tiles, not the grid)
-  if (q_full > 0) launch_x<AN, BN>(sched, wide, q_full, stream, a, b, c, M, N, K, lda, ldb, ldc);
-  const dim3 grid(2 * (nwg - q_full));
-  if (sched == 1)
-    MXK_LAUNCH_GEMM((mxk_gemm_bf16_x2_kernel<AN, BN, 0, 1, true>), grid, dim3(XT), stream, a,
-                       b, c, M, N, K, lda, ldb, ldc, nullptr, ws, q_full);
-  else
-    MXK_LAUNCH_GEMM((mxk_gemm_bf16_x2_kernel<AN, BN, 0, 0, true>), grid, dim3(XT), stream, a,
-                       b, c, M, N, K, lda, ldb, ldc, nullptr, ws, q_full);
-  hipLaunchKernelGGL(mxk_gemm_split_fixup, dim3(XBM * XBM / (256 * 8), nwg - q_full), dim3(256), 0,
-                     stream, ws, c, M, N, ldc, q_full);
-}
-}  // namespace
-
-// Bytes of fp32 workspace the split tail of an (M, N) output needs at most
-// (half a round of tiles, two partial tiles each).
-MXK_API long mxk_gemm_bf16_split_workspace(void) {
-  return static_cast<long>(hw_cus() / 2) * 2 * XBM * XBM * 4;   // any reservation fits
-}
-
-// mxk_gemm_bf16_ex (variant 1) with the split tail: when the output's 256^2
-// tiles fill q whole rounds of the CUs plus a last round at most half full
-// (e.g. 384 tiles on 256 CUs), the tail tiles run as K halves on twice as
-// many workgroups (fp32 partials in ws, summed by a fixup kernel) instead of
-// leaving half the chip idle for a whole round.  Layouts other than both
-// K-major only; every other case runs mxk_gemm_bf16_ex unchanged.  `ws`
-// holds >= ws_bytes (mxk_gemm_bf16_split_workspace()); sets *split to 1
-// when the split path ran.
-MXK_API int mxk_gemm_bf16_ex_ws(const void* A, const void* B, void* C, int M, int N, int K, int lda,
-                                int ldb, int ldc, int a_kmajor, int b_kmajor, void* ws,
-                                long ws_bytes, int* split, hipStream_t stream) {
-  if (split) *split = 0;
-  const int cus = device_cus();
-  const long nwg = M > 0 && N > 0 ? static_cast<long>(M / XBM) * (N / XBM) : 0;
-  long q_plan = nwg;
-  const int tail = static_cast<int>(mxk_gemm_split_plan(nwg, K, cus, &q_plan));
-  const bool want = tail > 0 && ws != nullptr &&
-                    ws_bytes >= static_cast<long>(2 * tail) * XBM * XBM * 4 &&
-                    reinterpret_cast<uintptr_t>(ws) % 16 == 0;
-  if (!want)
-    return mxk_gemm_bf16_ex_variant(A, B, C, M, N, K, lda, ldb, ldc, a_kmajor, b_kmajor, 1, stream);
-  const auto bytes = [](long rows, long ld) { return rows * ld * 2; };
-  const bool ok = M % XBM == 0 && N % XBM == 0 && lda % 8 == 0 && ldb % 8 == 0 && ldc % 4 == 0 &&
-                  (a_kmajor ? lda >= K : lda >= M) && (b_kmajor ? ldb >= K : ldb >= N) &&
-                  ldc >= N && (a_kmajor || bytes(K, lda) < (1L << 32)) &&
-                  (b_kmajor || bytes(K, ldb) < (1L << 32)) &&
-                  reinterpret_cast<uintptr_t>(A) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(B) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(C) % 8 == 0;
-  if (!ok) return static_cast<int>(hipErrorInvalidValue);
-  const int sched = (!a_kmajor && !b_kmajor) ? 1 : 0;
-  const bool wide = (ldc % 8 == 0) && (reinterpret_cast<uintptr_t>(C) % 16 == 0);
-  const int q_full = static_cast<int>(nwg) - tail;
-  auto a = static_cast<const uint16_t*>(A);
-  auto b = static_cast<const uint16_t*>(B);
-  auto c = static_cast<uint16_t*>(C);
-  auto w = static_cast<float*>(ws);
-  if (a_kmajor && b_kmajor)   // forward y = x W^T: the TN tail
-    launch_split<false, false>(sched, wide, nwg, q_full, stream, a, b, c, M, N, K, lda, ldb, ldc, w);
-  else if (a_kmajor)
-    launch_split<false, true>(sched, wide, nwg, q_full, stream, a, b, c, M, N, K, lda, ldb, ldc, w);
-  else if (b_kmajor)
-    launch_split<true, false>(sched, wide, nwg, q_full, stream, a, b, c, M, N, K, lda, ldb, ldc, w);
-  else
-    launch_split<true, true>(sched, wide, nwg, q_full, stream, a, b, c, M, N, K, lda, ldb, ldc, w);
-  if (split) *split = 1;
-  MXK_RETURN_LAUNCH_STATUS();
-}
-
-MXK_API int mxk_gemm_bf16_ex(const void* A, const void* B, void* C, int M, int N, int K, int lda,
-                             int ldb, int ldc, int a_kmajor, int b_kmajor, hipStream_t stream) {
-  return mxk_gemm_bf16_ex_variant(A, B, C, M, N, K, lda, ldb, ldc, a_kmajor, b_kmajor, 1, stream);
-}

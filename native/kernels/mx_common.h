@@ -6,7 +6,32 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+#include <cstdlib>
+
 #define MXK_API extern "C" __attribute__((visibility("default")))
+
+// Runs the statement with NAME a constexpr bool equal to the run-time `flag`,
+// so one launch with NAME among its template arguments stands for
+// `if (flag) launch<true, ..> else launch<false, ..>`.
+#define MXK_WITH_BOOL(NAME, flag, ...) \
+  do {                                 \
+    if (flag) {                        \
+      constexpr bool NAME = true;      \
+      __VA_ARGS__;                     \
+    } else {                           \
+      constexpr bool NAME = false;     \
+      __VA_ARGS__;                     \
+    }                                  \
+  } while (0)
+
+// A/B records (further schedules, epilogues, orders) are compiled only into
+// `make gemm-exp`'s library
+#ifdef MXK_GEMM_EXPERIMENTS
+constexpr bool kMxkExperiments = true;
+#else
+constexpr bool kMxkExperiments = false;
+#endif
 
 // Dynamic LDS to add to a one-workgroup-per-CU GEMM launch so that it claims
 // the CU's whole LDS while exclusive mode is on (mxk_gemm_set_exclusive,
@@ -820,7 +845,36 @@ struct SchedOneBarrierSpread : SchedOneBarrier {
   }
 };
 
+// An integer run-time knob (host only): the environment variable `env`, read
+// once on first use, or what set() stored since.  `fix` (a named function, not
+// a lambda: namespace-scope lambdas of one file can share a symbol; null: the
+// raw value) is applied to both; `dflt` stands for an unset variable.  A negative stored
+// value means "not read yet", so a knob that keeps raw values reads a negative
+// one again on every get().
+struct EnvKnob {
+  const char* env;
+  int dflt;
+  int (*fix)(int);
+  std::atomic<int> v{-1};
+  int get() {
+    int x = v.load(std::memory_order_relaxed);
+    if (x < 0) {
+      const char* e = std::getenv(env);
+      x = !e ? dflt : fix ? fix(std::atoi(e)) : std::atoi(e);
+      v.store(x, std::memory_order_relaxed);
+    }
+    return x;
+  }
+  void set(int x) { v.store(fix ? fix(x) : x); }
+};
+
 }  // namespace mxk
+
+namespace {
+// the bf16 view of an entry point's untyped tensor argument
+inline const uint16_t* bf(const void* p) { return static_cast<const uint16_t*>(p); }
+inline uint16_t* bf(void* p) { return static_cast<uint16_t*>(p); }
+}  // namespace
 
 // Host-side error plumbing: every launcher returns hipError_t as int so the
 // Python (ctypes) side can raise with the HIP error string.

@@ -4,6 +4,7 @@
     python scripts/isa_stream.py native/kernels/gemm_mxfp8.hip [extra hipcc flags]
     python scripts/isa_stream.py native/kernels/gemm_mxfp8.hip --diff OTHER.s
     python scripts/isa_stream.py native/kernels/gemm_mxfp8.hip --save NEW.s
+    python scripts/isa_stream.py native/kernels/gemm_bf16_layouts.hip --diff OTHER.s --by-name
 
 Compiles SOURCE with the Makefile's HIPFLAGS plus ``--cuda-device-only -S`` (a
 ``.s`` file is read as it is) and prints, for every kernel in file order, its
@@ -11,7 +12,11 @@ name, the register / LDS / scratch / spill metadata and the SHA-256 of its
 normalised instruction stream: the text between the kernel's label and its
 ``.Lfunc_end``, without comments, assembler directives, blank lines, label
 definitions and trailing ``; ...`` remarks.  Branch operands keep their label
-names, so two sources compare equal only with their kernels in the same order.
+names, so two sources compare equal only with their kernels in the same order;
+``--by-name`` drops the function number from those labels (``.LBB<f>_<n>``
+becomes ``.LBB_<n>``) and compares kernels by name alone, for a change that
+moves a template's first point of instantiation: it then lists the kernels
+whose position in the file changed.
 
 A refactor that must not move an instruction shows it by equal hashes against
 the listing of the parent commit's source; ``--diff`` prints where two
@@ -58,7 +63,7 @@ def listing(source: str, extra: list[str], save: str | None) -> str:
         return open(out).read()
 
 
-def kernels(asm: str) -> list[tuple[str, dict[str, str], list[str]]]:
+def kernels(asm: str, by_name: bool = False) -> list[tuple[str, dict[str, str], list[str]]]:
     """(name, metadata, normalised stream) of every kernel, in file order."""
     meta: dict[str, dict[str, str]] = {}
     entry: dict[str, str] = {}
@@ -82,7 +87,8 @@ def kernels(asm: str) -> list[tuple[str, dict[str, str], list[str]]]:
                 break
             body = body.split(";", 1)[0].strip()
             if body and not body.startswith(".") and not re.fullmatch(r"[\w$.]+:", body):
-                stream.append(re.sub(r"\s+", " ", body))
+                body = re.sub(r"\s+", " ", body)
+                stream.append(re.sub(r"\.LBB\d+_", ".LBB_", body) if by_name else body)
         found.append((m.group(1), meta[m.group(1)], stream))
     return found
 
@@ -127,11 +133,21 @@ def main() -> int:
     ap.add_argument("--save", metavar="OUT.s", help="keep the compiled listing")
     ap.add_argument("--vector-sequence", action="store_true",
                     help="also hash the mnemonics without scalar ALU and scalar moves")
+    ap.add_argument("--by-name", action="store_true",
+                    help="labels without their function number; kernels may change position")
     ap.add_argument("--context", type=int, default=8, help="lines shown by --diff")
     args, extra = ap.parse_known_args()
-    mine = kernels(listing(args.source, extra, args.save))
-    theirs = {n: (m, s) for n, m, s in kernels(open(args.diff).read())} if args.diff else {}
-    same = True
+    mine = kernels(listing(args.source, extra, args.save), args.by_name)
+    other = kernels(open(args.diff).read(), args.by_name) if args.diff else []
+    theirs = {n: (m, s) for n, m, s in other}
+    same = not args.diff or {n for n, _, _ in mine} == set(theirs)
+    for name in set(theirs) - {n for n, _, _ in mine}:
+        print(f"DIFF: {name} only in {args.diff}")
+    if args.diff and [n for n, _, _ in mine] != [n for n, _, _ in other]:
+        moved = [n for i, (n, _, _) in enumerate(mine) if i >= len(other) or other[i][0] != n]
+        print(f"kernel order differs from {args.diff} at {len(moved)} positions"
+              + ("" if args.by_name else " (branch labels carry the function number: --by-name)"))
+        same = same and args.by_name
     for (name, meta, stream), shown in zip(mine, demangle([n for n, _, _ in mine])):
         print(shown)
         print("  " + " ".join(f"{k}={meta.get(k, '?')}" for k in META_KEYS))

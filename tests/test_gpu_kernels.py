@@ -395,6 +395,62 @@ def test_gemm_split_tail_vs_fp32(cuda_device, layout, M, N, K):
     assert err <= 2 ** -7 * ref.abs().max().item() + 1e-3, err
 
 
+@pytest.mark.parametrize("layout", ["tn", "nn", "nt_wgrad", "tt"])
+def test_gemm_ex_ws_planned_routes_vs_fp32(cuda_device, layout):
+    """The routes of mxk_gemm_bf16_ex_ws a slip of the plan (gemm_plan.h) would
+    break, at the smallest shapes that reach them, for every operand layout
+    (both-K-major included: its split runs whole tiles on x2).  With all but 4
+    CUs reserved, 512 x 768 is 6 tiles = 4 whole + a tail of 2 as K halves; on
+    the whole chip 256 x 256 is 1 tile, all split (no whole-tile launch); at
+    K = 960 (not whole K-tile pairs) nothing splits and variant 1's route runs.
+    The split flag and the result against fp32, and the exported plan of each
+    call against the row expected here."""
+    import ctypes
+
+    from mxk8s.ops import _lib, gemm
+    from mxk8s.ops.gemm import _split_workspace
+    L = _lib.lib()
+    ak, bk = {"tn": (1, 1), "nn": (1, 0), "tt": (0, 1), "nt_wgrad": (0, 0)}[layout]
+    hb = int(layout == "nt_wgrad")
+    v1 = {"tn": (0, 0), "nt_wgrad": (2, 1)}.get(layout, (2, 0))       # (GemmFamily, schedule bit)
+    exp = L.mxk_gemm_bf16_ex_variant_built(4)
+    ws = _split_workspace(cuda_device)
+    gemm.set_reserved_cus(0)
+    hw = gemm.available_cus()
+    # (reserved CUs, M, N, K) -> family, schedule bit, grid, tail, q_full, split
+    cases = [((hw - 4, 512, 768, 1024), (2, hb, 4, 2, 4, 1)),
+             ((0, 256, 256, 1024), (2, hb, 0, 1, 0, 1)),
+             ((0, 256, 256, 960), (*v1, 1, 0, 1, 0))]
+    try:
+        L.mxk_gemm_x2_set_order(0)
+        for i, ((reserved, M, N, K), want) in enumerate(cases):
+            gemm.set_reserved_cus(reserved)
+            cus = gemm.available_cus()
+            assert cus == hw - reserved
+            a = _rand((M, K) if ak else (K, M), cuda_device, 81 + i).bfloat16()
+            b = _rand((N, K) if bk else (K, N), cuda_device, 91 + i).bfloat16()
+            ref = (a.float() if ak else a.float().t()) @ (b.float().t() if bk else b.float())
+            out = torch.full((M, N), float("nan"), device=cuda_device, dtype=torch.bfloat16)
+            plan = (ctypes.c_long * 9)()
+            assert L.mxk_gemm_bf16_ex_plan(M, N, K, a.stride(0), b.stride(0), N, ak, bk,
+                                           a.data_ptr() % 16, b.data_ptr() % 16, out.data_ptr() % 16,
+                                           1, cus, 0, exp, ws.data_ptr() % 16, ws.numel(), plan) == 0
+            family, sched, order, wide, grid, tail, q_full, ws_need, planned_split = plan
+            assert (family, sched, grid, tail, q_full, planned_split) == want, (layout, M, N, K)
+            assert (order, wide) == (0, 1) and ws_need == 2 * tail * 256 * 256 * 4 <= ws.numel()
+            split = ctypes.c_int(-1)
+            _lib.check(L.mxk_gemm_bf16_ex_ws(a.data_ptr(), b.data_ptr(), out.data_ptr(), M, N, K,
+                                             a.stride(0), b.stride(0), N, ak, bk, ws.data_ptr(),
+                                             ws.numel(), ctypes.byref(split),
+                                             _lib.stream_ptr(cuda_device)), "mxk_gemm_bf16_ex_ws")
+            torch.cuda.synchronize()
+            assert split.value == want[-1], (layout, M, N, K)
+            err = (out.float() - ref).abs().max().item()
+            assert err <= 2 ** -7 * ref.abs().max().item() + 1e-3, (layout, M, N, K, err)
+    finally:
+        gemm.set_reserved_cus(0)
+
+
 @pytest.mark.parametrize("T,V", [(4, 128256), (300, 1000), (7, 8)])
 def test_fused_cross_entropy_vs_fp32(cuda_device, T, V):
     from mxk8s.ops.xent import cross_entropy
