@@ -14,6 +14,7 @@
 #   make test-gemm-plan       the bf16 GEMM plans' sweep, hostile integers included (host, ASan+UBSan build)
 #   make test-attention-doc   the document-mask predicate and tile bounds (host, ASan+UBSan build)
 #   make test-mxfp4-format    the e2m1 conversion and block exponent over every bf16 (host, ASan+UBSan build)
+#   make test-gemm-bench-report  mx-gemm-bench's RESULT lines, pass rule and spot block (host, ASan+UBSan build)
 #
 # Everything lands inside the repo so `gpurun` snapshots carry it to the box.
 
@@ -43,7 +44,7 @@ NODE_SRCS := $(wildcard native/libmxnode/*.cc)
 NODE_OBJS := $(patsubst native/libmxnode/%.cc,$(BUILD)/node/%.o,$(NODE_SRCS))
 NODE_HDRS := $(wildcard native/libmxnode/*.h)
 
-.PHONY: all kernels gemm-exp node tools clean test-native test-native-tsan test-attention-plan test-gemm-plan test-attention-doc test-mxfp4-format fake-amdsmi
+.PHONY: all kernels gemm-exp node tools clean test-native test-native-tsan test-attention-plan test-gemm-plan test-attention-doc test-mxfp4-format test-gemm-bench-report fake-amdsmi
 all: kernels node tools fake-amdsmi
 
 kernels: $(OUT_LIB)/libmxkernels.so
@@ -96,6 +97,8 @@ tools: $(OUT_BIN)/mx-vector-add $(OUT_BIN)/mx-gemm-bench $(OUT_BIN)/mx-allreduce
 $(BUILD)/tools/%.o: native/tools/%.hip $(KERNEL_HDRS)
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(BUILD)/tools/gemm_bench_main.o: native/tools/gemm_bench_report.h
 
 $(BUILD)/tools/allreduce_perf.o: native/rccl_bench/allreduce_perf.cc native/rccl_bench/sweep_plan.h
 	@mkdir -p $(dir $@)
@@ -169,6 +172,14 @@ $(BUILD)/asan/mxfp4_format_sweep: native/kernels/tests/mxfp4_format_sweep.cc nat
 	@mkdir -p $(dir $@)
 	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -Wshadow -fsanitize=address,undefined -fno-sanitize-recover=all \
 	    -fno-omit-frame-pointer -Inative/kernels -o $@ $<
+
+test-gemm-bench-report: $(BUILD)/asan/gemm_bench_report_test
+	$<
+
+$(BUILD)/asan/gemm_bench_report_test: native/tools/tests/gemm_bench_report_test.cc native/tools/gemm_bench_report.h
+	@mkdir -p $(dir $@)
+	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -Wshadow -fsanitize=address,undefined -fno-sanitize-recover=all \
+	    -fno-omit-frame-pointer -Inative/tools -o $@ $<
 
 clean:
 	rm -rf $(BUILD) $(OUT_LIB)/*.so $(OUT_BIN)

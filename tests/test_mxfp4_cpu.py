@@ -1,17 +1,16 @@
 """MXFP4 (block-scaled e2m1) path, everything that needs no GPU: the reference
 quantiser, the op's contract, validator plumbing, build hygiene of
 ``native/kernels/gemm_mxfp4.hip`` and the host sweep of ``mxfp4_format.h``."""
-import json
 import os
 import re
 import shutil
-import stat
 import subprocess
 
 import pytest
 import torch
 
 import mxk8s.validate.__main__ as V
+from mx_gemm_checks import fake_bench, run_validator
 from mxk8s.ops import _lib
 from mxk8s.ops.mxfp4 import (dequantize_mxfp4, gemm_mxfp4_tn, is_fast_shape_mxfp4, quantize_mxfp4,
                              quantize_mxfp4_ref)
@@ -271,44 +270,11 @@ def test_fp4_error_against_the_bf16_product_is_the_formats_own():
 
 
 # ---- validator plumbing ---------------------------------------------------------
-BF16_LINE = ('{"test":"gemm","gpu":0,"M":4096,"N":4096,"K":4096,"dtype":"bf16","median_ms":0.1,'
-             '"min_ms":0.1,"tflops":1300.0,"rel_err_vs_rocblas":0.001,"spot_block":[0,0],'
-             '"max_abs_err":0.1,"spot_tolerance":0.5,"pass":true}')
-
-
-def _mx_line(dtype, tflops, ok=True):
-    return ('{"test":"gemm","gpu":0,"M":4096,"N":4096,"K":4096,"dtype":"%s","median_ms":0.05,'
-            '"min_ms":0.05,"tflops":%s,"rel_err_vs_rocblas":null,"spot_block":[0,0],'
-            '"max_abs_err":0.1,"spot_tolerance":0.5,"quantize_ms":0.1,"pass":%s}'
-            % (dtype, tflops, "true" if ok else "false"))
-
-
-def _fake_bench(tmp_path, fp4_pass=True, fp4_rc=0):
-    p = tmp_path / "mx-gemm-bench"
-    p.write_text("#!/bin/sh\n"
-                 f'echo "$@" >> {tmp_path}/calls\n'
-                 'case "$*" in\n'
-                 f"  *mxfp4*) echo 'RESULT {_mx_line('mxfp4', 4000.0, fp4_pass)}'; exit {fp4_rc};;\n"
-                 f"  *mxfp8*) echo 'RESULT {_mx_line('mxfp8', 2500.0)}';;\n"
-                 f"  *) echo 'RESULT {BF16_LINE}';;\n"
-                 "esac\n")
-    p.chmod(p.stat().st_mode | stat.S_IEXEC)
-
-
-def _run_validator(tmp_path, monkeypatch, capsys, argv):
-    monkeypatch.setattr(V, "BIN", str(tmp_path))
-    monkeypatch.setattr(V, "_extra_env", {})
-    rc = V.main(argv)
-    rs = [json.loads(l[7:]) for l in capsys.readouterr().out.splitlines() if l.startswith("RESULT ")]
-    calls = (tmp_path / "calls").read_text().splitlines()
-    return rc, rs, calls
-
-
 def test_validator_three_dtypes_three_runs_two_tagged_summaries(tmp_path, monkeypatch, capsys):
-    _fake_bench(tmp_path)
-    rc, rs, calls = _run_validator(tmp_path, monkeypatch, capsys,
-                                   ["--tests", "gemm", "--gemm-dtypes", "bf16,mxfp8,mxfp4",
-                                    "--gemm-sizes", "4096"])
+    fake_bench(tmp_path)
+    rc, rs, calls = run_validator(tmp_path, monkeypatch, capsys,
+                                  ["--tests", "gemm", "--gemm-dtypes", "bf16,mxfp8,mxfp4",
+                                   "--gemm-sizes", "4096"])
     assert rc == 0
     assert calls == ["--sizes 4096 --devices all", "--sizes 4096 --devices all --dtype mxfp8",
                      "--sizes 4096 --devices all --dtype mxfp4"]
@@ -323,9 +289,9 @@ def test_validator_three_dtypes_three_runs_two_tagged_summaries(tmp_path, monkey
 
 @pytest.mark.parametrize("fp4_rc", [0, 1])
 def test_validator_fails_on_a_failing_mxfp4_line(tmp_path, monkeypatch, capsys, fp4_rc):
-    _fake_bench(tmp_path, fp4_pass=False, fp4_rc=fp4_rc)
-    rc, rs, _ = _run_validator(tmp_path, monkeypatch, capsys,
-                               ["--tests", "gemm", "--gemm-dtypes", "bf16,mxfp8,mxfp4"])
+    fake_bench(tmp_path, "mxfp4", ok=False, rc=fp4_rc)
+    rc, rs, _ = run_validator(tmp_path, monkeypatch, capsys,
+                              ["--tests", "gemm", "--gemm-dtypes", "bf16,mxfp8,mxfp4"])
     assert rc == 1
     assert rs[-1]["test"] == "validator" and rs[-1]["pass"] is False
     summ = {r.get("dtype"): r for r in rs if r["test"] == "gemm_summary"}
@@ -333,16 +299,16 @@ def test_validator_fails_on_a_failing_mxfp4_line(tmp_path, monkeypatch, capsys, 
 
 
 def test_validator_fails_on_a_nonzero_exit_with_a_passing_line(tmp_path, monkeypatch, capsys):
-    _fake_bench(tmp_path, fp4_pass=True, fp4_rc=3)
-    rc, rs, _ = _run_validator(tmp_path, monkeypatch, capsys,
-                               ["--tests", "gemm", "--gemm-dtypes", "mxfp4"])
+    fake_bench(tmp_path, "mxfp4", ok=True, rc=3)
+    rc, rs, _ = run_validator(tmp_path, monkeypatch, capsys,
+                              ["--tests", "gemm", "--gemm-dtypes", "mxfp4"])
     assert rc == 1 and rs[-1]["pass"] is False
 
 
 def test_validator_mxfp4_alone(tmp_path, monkeypatch, capsys):
-    _fake_bench(tmp_path)
-    rc, rs, calls = _run_validator(tmp_path, monkeypatch, capsys,
-                                   ["--tests", "gemm", "--gemm-dtypes", "mxfp4", "--gemm-sizes", "4096"])
+    fake_bench(tmp_path)
+    rc, rs, calls = run_validator(tmp_path, monkeypatch, capsys,
+                                  ["--tests", "gemm", "--gemm-dtypes", "mxfp4", "--gemm-sizes", "4096"])
     assert rc == 0 and calls == ["--sizes 4096 --devices all --dtype mxfp4"]
     assert [r["test"] for r in rs] == ["gemm", "gemm_summary", "validator"]
     assert rs[1]["dtype"] == "mxfp4"

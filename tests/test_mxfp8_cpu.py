@@ -5,13 +5,13 @@ import json
 import os
 import re
 import shutil
-import stat
 import subprocess
 
 import pytest
 import torch
 
 import mxk8s.validate.__main__ as V
+from mx_gemm_checks import BF16_LINE, fake_bench, run_validator
 from mxk8s import config
 from mxk8s.chart import render
 from mxk8s.ops import _lib
@@ -213,38 +213,9 @@ def test_fp8_error_against_the_bf16_product_is_the_formats_own():
 
 
 # ---- validator plumbing ---------------------------------------------------------
-BF16_LINE = ('{"test":"gemm","gpu":0,"M":4096,"N":4096,"K":4096,"dtype":"bf16","median_ms":0.1,'
-             '"min_ms":0.1,"tflops":1300.0,"rel_err_vs_rocblas":0.001,"spot_block":[0,0],'
-             '"max_abs_err":0.1,"spot_tolerance":0.5,"pass":true}')
-
-
-def _fake_bench(tmp_path, mx_pass=True, mx_rc=0):
-    mx = ('{"test":"gemm","gpu":0,"M":4096,"N":4096,"K":4096,"dtype":"mxfp8","median_ms":0.05,'
-          '"min_ms":0.05,"tflops":2500.0,"rel_err_vs_rocblas":null,"spot_block":[0,0],'
-          '"max_abs_err":0.1,"spot_tolerance":0.5,"quantize_ms":0.1,"pass":%s}'
-          % ("true" if mx_pass else "false"))
-    p = tmp_path / "mx-gemm-bench"
-    p.write_text("#!/bin/sh\n"
-                 f'echo "$@" >> {tmp_path}/calls\n'
-                 'case "$*" in\n'
-                 f"  *mxfp8*) echo 'RESULT {mx}'; exit {mx_rc};;\n"
-                 f"  *) echo 'RESULT {BF16_LINE}';;\n"
-                 "esac\n")
-    p.chmod(p.stat().st_mode | stat.S_IEXEC)
-
-
-def _run_validator(tmp_path, monkeypatch, capsys, argv):
-    monkeypatch.setattr(V, "BIN", str(tmp_path))
-    monkeypatch.setattr(V, "_extra_env", {})
-    rc = V.main(argv)
-    rs = [json.loads(l[7:]) for l in capsys.readouterr().out.splitlines() if l.startswith("RESULT ")]
-    calls = (tmp_path / "calls").read_text().splitlines()
-    return rc, rs, calls
-
-
 def test_validator_default_runs_bf16_once_with_todays_lines(tmp_path, monkeypatch, capsys):
-    _fake_bench(tmp_path)
-    rc, rs, calls = _run_validator(tmp_path, monkeypatch, capsys, ["--tests", "gemm"])
+    fake_bench(tmp_path)
+    rc, rs, calls = run_validator(tmp_path, monkeypatch, capsys, ["--tests", "gemm"])
     assert rc == 0
     assert calls == ["--sizes 4096,8192,16384 --devices all"]
     assert rs[0] == json.loads(BF16_LINE)
@@ -255,10 +226,10 @@ def test_validator_default_runs_bf16_once_with_todays_lines(tmp_path, monkeypatc
 
 
 def test_validator_two_dtypes_two_runs_two_summaries(tmp_path, monkeypatch, capsys):
-    _fake_bench(tmp_path)
-    rc, rs, calls = _run_validator(tmp_path, monkeypatch, capsys,
-                                   ["--tests", "gemm", "--gemm-dtypes", "bf16,mxfp8",
-                                    "--gemm-sizes", "4096"])
+    fake_bench(tmp_path)
+    rc, rs, calls = run_validator(tmp_path, monkeypatch, capsys,
+                                  ["--tests", "gemm", "--gemm-dtypes", "bf16,mxfp8",
+                                   "--gemm-sizes", "4096"])
     assert rc == 0
     assert calls == ["--sizes 4096 --devices all", "--sizes 4096 --devices all --dtype mxfp8"]
     summ = [r for r in rs if r["test"] == "gemm_summary"]
@@ -271,9 +242,9 @@ def test_validator_two_dtypes_two_runs_two_summaries(tmp_path, monkeypatch, caps
 
 @pytest.mark.parametrize("mx_rc", [0, 1])
 def test_validator_fails_on_a_failing_mxfp8_line(tmp_path, monkeypatch, capsys, mx_rc):
-    _fake_bench(tmp_path, mx_pass=False, mx_rc=mx_rc)
-    rc, rs, _ = _run_validator(tmp_path, monkeypatch, capsys,
-                               ["--tests", "gemm", "--gemm-dtypes", "bf16,mxfp8"])
+    fake_bench(tmp_path, "mxfp8", ok=False, rc=mx_rc)
+    rc, rs, _ = run_validator(tmp_path, monkeypatch, capsys,
+                              ["--tests", "gemm", "--gemm-dtypes", "bf16,mxfp8"])
     assert rc == 1
     assert rs[-1]["test"] == "validator" and rs[-1]["pass"] is False
     assert [r for r in rs if r.get("dtype") == "mxfp8" and r["test"] == "gemm_summary"][0]["pass"] is False
