@@ -46,10 +46,10 @@ class LlamaConfig:
     norm_eps: float = 1e-5
     rope_theta: float = 500000.0
     max_seq_len: int = 8192
-    # "mxfp8" (opt-in): wqkv, wo, w13 and w2 run their three products on the
-    # MXFP8 GEMM (mxk8s.ops.linear.linear_mxfp8) without the fused RoPE / SwiGLU
-    # epilogues, which are bf16 kernels; lm_head and everything that is not a
-    # linear layer stay bf16
+    # "mxfp8" / "mxfp4" (opt-in): wqkv, wo, w13 and w2 run their three products
+    # on the MXFP8 / MXFP4 GEMM (mxk8s.ops.linear.linear_mxfp8, linear_mxfp4)
+    # without the fused RoPE / SwiGLU epilogues, which are bf16 kernels; lm_head
+    # and everything that is not a linear layer stay bf16
     linear_dtype: str = "bf16"
 
     def __post_init__(self):
@@ -127,7 +127,7 @@ class Attention(nn.Module):
             return self.wo(o.transpose(1, 2).reshape(B, S, c.n_heads * hd))
         # projection + RoPE (in the GEMM's epilogue) + flash attention as one
         # node; its backward takes d(qkv) from the attention kernels with the
-        # RoPE backward fused into their stores (a bf16 GEMM: not with mxfp8 linears)
+        # RoPE backward fused into their stores (a bf16 GEMM: not with MX linears)
         o = None
         if c.linear_dtype == "bf16":
             o = proj_rope_attention(x, self.wqkv.weight, cos, sin, c.n_heads, c.n_kv_heads, hd)
@@ -154,14 +154,14 @@ class Attention(nn.Module):
 class MLP(nn.Module):
     def __init__(self, cfg: LlamaConfig):
         super().__init__()
-        self.mxfp8 = cfg.linear_dtype == "mxfp8"
+        self.bf16_linears = cfg.linear_dtype == "bf16"
         self.w13 = Linear(cfg.dim, 2 * cfg.ffn_dim, compute=cfg.linear_dtype)   # [gate | up]
         # w2(swiglu(.)) as one node: the SwiGLU backward runs in the epilogue
         # of w2's input-gradient GEMM
         self.w2 = SwiGLULinear(cfg.ffn_dim, cfg.dim, compute=cfg.linear_dtype)
 
     def forward(self, x):
-        if x.is_cuda and x.dtype == torch.bfloat16 and not self.mxfp8:
+        if x.is_cuda and x.dtype == torch.bfloat16 and self.bf16_linears:
             # one node: up-projection with SwiGLU in its epilogue, down
             # projection, fused dgrad-SwiGLU backward (mxk8s.ops.linear)
             return swiglu_mlp(x, self.w13.weight, self.w2.weight)

@@ -6,16 +6,18 @@
   :func:`quantize_mxfp8_t`, :func:`quantize_mxfp8_dual` — the transposing quantiser,
   :func:`linear_mxfp8` — a linear layer's three products on that GEMM (opt-in)
 * :func:`quantize_mxfp4`, :func:`gemm_mxfp4_tn` — MXFP4 (block-scaled e2m1, two codes per
-  byte) quantiser and scaled-MFMA GEMM (validator config 3, ``--gemm-dtypes mxfp4``)
+  byte) quantiser and scaled-MFMA GEMM (validator config 3, ``--gemm-dtypes mxfp4``);
+  :func:`quantize_mxfp4_t`, :func:`quantize_mxfp4_dual` — the transposing quantiser,
+  :func:`linear_mxfp4` — a linear layer's three products on that GEMM (opt-in)
 * :func:`vector_add`    — smoke-test payload (config 2)
 * :func:`rmsnorm`, :func:`swiglu`, :func:`rope` — fused training ops (config 5)
 """
 from .gemm import gemm_bf16_tn, gemm_flops, is_fast_shape
 from .mxfp8 import (quantize_mxfp8, quantize_mxfp8_ref, quantize_mxfp8_t, quantize_mxfp8_dual,
                     dequantize_mxfp8, gemm_mxfp8_tn, is_fast_shape_mxfp8)
-from .mxfp4 import (quantize_mxfp4, quantize_mxfp4_ref, dequantize_mxfp4, gemm_mxfp4_tn,
-                    is_fast_shape_mxfp4)
-from .linear import linear_mxfp8, is_mxfp8_linear_shape
+from .mxfp4 import (quantize_mxfp4, quantize_mxfp4_ref, quantize_mxfp4_t, quantize_mxfp4_dual,
+                    dequantize_mxfp4, gemm_mxfp4_tn, is_fast_shape_mxfp4)
+from .linear import linear_mxfp8, is_mxfp8_linear_shape, linear_mxfp4, is_mxfp4_linear_shape
 from .vector_add import vector_add
 from .fused import rmsnorm, swiglu, rope, rope_tables
 from ._lib import kernels_available, KERNEL_LIB_PATH
@@ -23,5 +25,6 @@ from ._lib import kernels_available, KERNEL_LIB_PATH
 __all__ = ["gemm_bf16_tn", "gemm_flops", "is_fast_shape", "quantize_mxfp8", "quantize_mxfp8_ref",
            "quantize_mxfp8_t", "quantize_mxfp8_dual", "linear_mxfp8", "is_mxfp8_linear_shape",
            "dequantize_mxfp8", "gemm_mxfp8_tn", "is_fast_shape_mxfp8", "quantize_mxfp4",
-           "quantize_mxfp4_ref", "dequantize_mxfp4", "gemm_mxfp4_tn", "is_fast_shape_mxfp4", "vector_add", "rmsnorm", "swiglu",
-           "rope", "rope_tables", "kernels_available", "KERNEL_LIB_PATH"]
+           "quantize_mxfp4_ref", "quantize_mxfp4_t", "quantize_mxfp4_dual", "linear_mxfp4",
+           "is_mxfp4_linear_shape", "dequantize_mxfp4", "gemm_mxfp4_tn", "is_fast_shape_mxfp4",
+           "vector_add", "rmsnorm", "swiglu", "rope", "rope_tables", "kernels_available", "KERNEL_LIB_PATH"]

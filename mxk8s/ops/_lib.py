@@ -59,6 +59,8 @@ _SIGNATURES = {
     "mxk_gemm_mxfp4_tn": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "mxk_gemm_mxfp4_tn_is_fast": (_i, [_i, _i, _i]),
     "mxk_quantize_mxfp4": (_i, [_vp, _vp, _vp, _l, _i, _l, _l, _l, _vp]),
+    "mxk_quantize_mxfp4_t": (_i, [_vp, _vp, _vp, _l, _l, _l, _l, _l, _vp]),
+    "mxk_quantize_mxfp4_dual": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _l, _vp]),
     "mxk_gemm_bf16_ex": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "mxk_gemm_bf16_ex_variant": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "mxk_gemm_bf16_ex_ws": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _l,

@@ -26,6 +26,23 @@ def check_x(x: torch.Tensor) -> None:
         raise ValueError("x must be K-contiguous (stride(1) == 1)")
 
 
+def check_xt(x: torch.Tensor, dual: bool) -> None:
+    """The argument of a transposing quantiser: blocks of 32 along the rows."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("x must be a tensor")
+    if x.dtype != torch.bfloat16:
+        raise TypeError(f"x must be bfloat16, got {x.dtype}")
+    if x.dim() != 2:
+        raise ValueError(f"x must be 2-D, got shape {tuple(x.shape)}")
+    R, C = x.shape
+    if R == 0 or C == 0 or R % BLOCK or (dual and C % BLOCK):
+        raise ValueError(f"x must be [R, C] with R a positive multiple of {BLOCK} and C "
+                         + (f"a positive multiple of {BLOCK}" if dual else "> 0")
+                         + f", got {tuple(x.shape)}")
+    if x.stride(1) != 1:
+        raise ValueError("x must be row-major (stride(1) == 1)")
+
+
 def block_exponent(xb: torch.Tensor, emax: int) -> torch.Tensor:
     """``xb`` fp32 ``[R, K/32, 32]`` -> int32 ``[R, K/32]``: ``floor(log2(amax)) -
     emax`` clamped to [-127, 127], 0 for an all-zero block."""

@@ -108,15 +108,15 @@ class _LinearFn(torch.autograd.Function):
         return dx, dw
 
 
-# ---- MXFP8 (opt-in) ---------------------------------------------------------
-# gemm_mxfp8_tn contracts over the contiguous axis of both operands, and an MX
-# block lies along the contracted axis:
+# ---- MXFP8 and MXFP4 (opt-in) -----------------------------------------------
+# gemm_mxfp8_tn / gemm_mxfp4_tn contract over the contiguous axis of both
+# operands, and an MX block lies along the contracted axis:
 #   y  = x W^T      x [T, in] and W [out, in] quantised along their rows
 #   dx = dy W       dy [T, out] along its rows, W along its columns: the
-#                   transposed image quantize_mxfp8_t(W) [in, out]
-#   dW = dy^T x     both along the token axis: quantize_mxfp8_t(dy) [out, T]
-#                   and quantize_mxfp8_t(x) [in, T]
-# dy is read once for both of its images (quantize_mxfp8_dual).
+#                   transposed image quantize_<fmt>_t(W) [in, out]
+#   dW = dy^T x     both along the token axis: quantize_<fmt>_t(dy) [out, T]
+#                   and quantize_<fmt>_t(x) [in, T]
+# dy is read once for both of its images (quantize_<fmt>_dual).
 _MX_TILE = 256
 
 
@@ -127,6 +127,13 @@ def is_mxfp8_linear_shape(T: int, in_features: int, out_features: int) -> bool:
     return all(n > 0 and n % _MX_TILE == 0 for n in (T, in_features, out_features))
 
 
+def is_mxfp4_linear_shape(T: int, in_features: int, out_features: int) -> bool:
+    """True when ``linear_mxfp4`` takes the shape: tokens, in and out features
+    all positive multiples of 256, which gives M, N and K % 256 in each of the
+    three products."""
+    return is_mxfp8_linear_shape(T, in_features, out_features)
+
+
 def _bf16_rows(t: torch.Tensor) -> torch.Tensor:
     """bf16 and unit inner stride (a row stride larger than the width stays)."""
     if t.dtype != torch.bfloat16:
@@ -134,55 +141,95 @@ def _bf16_rows(t: torch.Tensor) -> torch.Tensor:
     return t if t.stride(1) == 1 else t.contiguous()
 
 
-def _mx_weight_grad(weight: torch.Tensor, dyt, xt):
-    """_weight_grad on the MXFP8 GEMM: dW = dequant(dy^T) dequant(x^T)^T."""
-    from .mxfp8 import gemm_mxfp8_tn
+def _mx_ops(fmt: str):
+    """(gemm_tn, quantize, quantize_t, quantize_dual) of "mxfp8" / "mxfp4", read
+    from the format's module at every call."""
+    if fmt == "mxfp8":
+        from . import mxfp8 as m
+    else:
+        from . import mxfp4 as m
+    return tuple(getattr(m, n.format(fmt)) for n in ("gemm_{}_tn", "quantize_{}", "quantize_{}_t",
+                                                     "quantize_{}_dual"))
+
+
+def _mx_weight_grad(weight: torch.Tensor, dyt, xt, gemm):
+    """_weight_grad on an MX GEMM: dW = dequant(dy^T) dequant(x^T)^T."""
     sink = getattr(weight, "main_grad", None)
     if sink is None:
-        return gemm_mxfp8_tn(*dyt, *xt).to(weight.dtype)
+        return gemm(*dyt, *xt).to(weight.dtype)
     if weight._mxk_grad_fresh:
         if sink.dtype == torch.bfloat16:
-            gemm_mxfp8_tn(*dyt, *xt, out=sink)
+            gemm(*dyt, *xt, out=sink)
         else:                                   # an fp32 flat buffer: the GEMM's output is bf16
-            sink.copy_(gemm_mxfp8_tn(*dyt, *xt))
+            sink.copy_(gemm(*dyt, *xt))
         weight._mxk_grad_fresh = False
     else:
-        sink.add_(gemm_mxfp8_tn(*dyt, *xt))
+        sink.add_(gemm(*dyt, *xt))
     ready = getattr(weight, "_mxk_grad_ready", None)
     if ready is not None:
         ready()
     return None
 
 
+def _mx_forward(fmt: str, ctx, x, weight):
+    gemm, quantize, _, _ = _mx_ops(fmt)
+    ctx.save_for_backward(x, weight)          # bf16, as _LinearFn: no quantised copy is held
+    x2 = _bf16_rows(x.reshape(-1, x.shape[-1]))
+    y = gemm(*quantize(x2), *quantize(_bf16_rows(weight)))
+    return y.to(x.dtype).view(*x.shape[:-1], weight.shape[0])
+
+
+def _mx_backward(fmt: str, ctx, dy):
+    gemm, quantize, quantize_t, quantize_dual = _mx_ops(fmt)
+    x, weight = ctx.saved_tensors
+    need_x, need_w = ctx.needs_input_grad
+    dy2 = _bf16_rows(dy.reshape(-1, dy.shape[-1]))
+    if need_x and need_w:
+        dq, ds, dqt, dst = quantize_dual(dy2)
+    elif need_x:
+        dq, ds = quantize(dy2)
+    elif need_w:
+        dqt, dst = quantize_t(dy2)
+    dx = dw = None
+    if need_x:
+        dx = gemm(dq, ds, *quantize_t(_bf16_rows(weight)))
+        dx = dx.to(x.dtype).view(x.shape)
+    if need_w:
+        x2 = _bf16_rows(x.reshape(-1, x.shape[-1]))
+        dw = _mx_weight_grad(weight, (dqt, dst), quantize_t(x2), gemm)
+    return dx, dw
+
+
 class _LinearMxfp8Fn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight):
-        from .mxfp8 import gemm_mxfp8_tn, quantize_mxfp8
-        ctx.save_for_backward(x, weight)      # bf16, as _LinearFn: no quantised copy is held
-        x2 = _bf16_rows(x.reshape(-1, x.shape[-1]))
-        y = gemm_mxfp8_tn(*quantize_mxfp8(x2), *quantize_mxfp8(_bf16_rows(weight)))
-        return y.to(x.dtype).view(*x.shape[:-1], weight.shape[0])
+        return _mx_forward("mxfp8", ctx, x, weight)
 
     @staticmethod
     def backward(ctx, dy):
-        from .mxfp8 import gemm_mxfp8_tn, quantize_mxfp8, quantize_mxfp8_dual, quantize_mxfp8_t
-        x, weight = ctx.saved_tensors
-        need_x, need_w = ctx.needs_input_grad
-        dy2 = _bf16_rows(dy.reshape(-1, dy.shape[-1]))
-        if need_x and need_w:
-            dq, ds, dqt, dst = quantize_mxfp8_dual(dy2)
-        elif need_x:
-            dq, ds = quantize_mxfp8(dy2)
-        elif need_w:
-            dqt, dst = quantize_mxfp8_t(dy2)
-        dx = dw = None
-        if need_x:
-            dx = gemm_mxfp8_tn(dq, ds, *quantize_mxfp8_t(_bf16_rows(weight)))
-            dx = dx.to(x.dtype).view(x.shape)
-        if need_w:
-            x2 = _bf16_rows(x.reshape(-1, x.shape[-1]))
-            dw = _mx_weight_grad(weight, (dqt, dst), quantize_mxfp8_t(x2))
-        return dx, dw
+        return _mx_backward("mxfp8", ctx, dy)
+
+
+class _LinearMxfp4Fn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight):
+        return _mx_forward("mxfp4", ctx, x, weight)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return _mx_backward("mxfp4", ctx, dy)
+
+
+def _mx_linear(name: str, fn, x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
+    if weight.dim() != 2 or x.dim() < 1 or x.shape[-1] != weight.shape[1]:
+        raise ValueError(f"{name}: x {tuple(x.shape)} does not match weight "
+                         f"{tuple(weight.shape)}")
+    T = x.numel() // x.shape[-1] if x.shape[-1] else 0
+    if not is_mxfp8_linear_shape(T, weight.shape[1], weight.shape[0]):
+        raise ValueError(f"{name} needs tokens, in_features and out_features to be positive "
+                         f"multiples of {_MX_TILE}, got T={T} in={weight.shape[1]} "
+                         f"out={weight.shape[0]}")
+    return fn.apply(x, weight)
 
 
 def linear_mxfp8(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
@@ -193,15 +240,23 @@ def linear_mxfp8(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
     quantising and the results returned in their own dtype.  The weight
     gradient keeps the ``main_grad`` contract of :class:`Linear`.  Raises
     ``ValueError`` unless :func:`is_mxfp8_linear_shape` holds."""
-    if weight.dim() != 2 or x.dim() < 1 or x.shape[-1] != weight.shape[1]:
-        raise ValueError(f"linear_mxfp8: x {tuple(x.shape)} does not match weight "
-                         f"{tuple(weight.shape)}")
-    T = x.numel() // x.shape[-1] if x.shape[-1] else 0
-    if not is_mxfp8_linear_shape(T, weight.shape[1], weight.shape[0]):
-        raise ValueError("linear_mxfp8 needs tokens, in_features and out_features to be positive "
-                         f"multiples of {_MX_TILE}, got T={T} in={weight.shape[1]} "
-                         f"out={weight.shape[0]}")
-    return _LinearMxfp8Fn.apply(x, weight)
+    return _mx_linear("linear_mxfp8", _LinearMxfp8Fn, x, weight)
+
+
+def linear_mxfp4(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
+    """``x @ weight.T`` whose forward product, input gradient and weight gradient
+    all run on the MXFP4 GEMM (``gemm_mxfp4_tn``), each operand quantised in
+    blocks of 32 along the axis its product contracts.  ``x`` is ``[..., in]``,
+    ``weight`` ``[out, in]``; tensors that are not bf16 are cast to bf16 for
+    quantising and the results returned in their own dtype.  The weight
+    gradient keeps the ``main_grad`` contract of :class:`Linear`.  Raises
+    ``ValueError`` unless :func:`is_mxfp4_linear_shape` holds.
+
+    All three products round to nearest even, like the rest of the MX code
+    here.  FP4 gradients under round-to-nearest-even are biased; the switch
+    changes the numerics of the step (e2m1's own error against the bf16
+    product is ~21 % per product), and no convergence run backs it yet."""
+    return _mx_linear("linear_mxfp4", _LinearMxfp4Fn, x, weight)
 
 
 # y = swiglu(gu) W^T with the SwiGLU backward fused into the input-gradient
@@ -320,9 +375,12 @@ class Linear(nn.Linear):
     ``compute="mxfp8"`` (opt-in) runs the three products of a call on the
     MXFP8 GEMM (:func:`linear_mxfp8`) when :func:`is_mxfp8_linear_shape` holds
     for it, i.e. tokens, in and out features are multiples of 256.  Any other
-    call (toy shapes, a ragged batch) silently takes the bf16 path."""
+    call (toy shapes, a ragged batch) silently takes the bf16 path.
+    ``compute="mxfp4"`` does the same with the MXFP4 GEMM
+    (:func:`linear_mxfp4`, :func:`is_mxfp4_linear_shape`)."""
 
-    COMPUTE = ("bf16", "mxfp8")
+    COMPUTE = ("bf16", "mxfp8", "mxfp4")
+    _MX_FN = {"mxfp8": _LinearMxfp8Fn, "mxfp4": _LinearMxfp4Fn}
 
     def __init__(self, in_features: int, out_features: int, compute: str = "bf16", **kw):
         if compute not in self.COMPUTE:
@@ -332,9 +390,10 @@ class Linear(nn.Linear):
         self.weight._mxk_direct_grad = True
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        if self.compute == "mxfp8" and is_mxfp8_linear_shape(
+        fn = self._MX_FN.get(self.compute)
+        if fn is not None and is_mxfp8_linear_shape(      # one predicate for both formats
                 x.numel() // self.in_features, self.in_features, self.out_features):
-            return _LinearMxfp8Fn.apply(x, self.weight)
+            return fn.apply(x, self.weight)
         return _LinearFn.apply(x, self.weight)
 
 
@@ -342,11 +401,11 @@ class SwiGLULinear(Linear):
     """Down projection applied to swiglu(gu), gu = [gate | up] of width
     2 * in_features: ``w2(swiglu(gu))`` as one node whose backward fuses the
     SwiGLU gradient into the input-gradient GEMM.  CPU / non-bf16 inputs take
-    the plain composition, and so does ``compute="mxfp8"``: the fused
-    dgrad-SwiGLU kernel is a bf16 kernel."""
+    the plain composition, and so does every ``compute`` but ``"bf16"``: the
+    fused dgrad-SwiGLU kernel is a bf16 kernel."""
 
     def forward(self, gu: torch.Tensor) -> torch.Tensor:
-        if gu.device.type == "cpu" or gu.dtype != torch.bfloat16 or self.compute == "mxfp8":
+        if gu.device.type == "cpu" or gu.dtype != torch.bfloat16 or self.compute != "bf16":
             from .fused import swiglu
             return super().forward(swiglu(gu))
         return _SwiGLULinearFn.apply(gu, self.weight)

@@ -1,4 +1,5 @@
-"""MXFP4 quantiser and block-scaled MFMA GEMM op (``native/kernels/gemm_mxfp4.hip``).
+"""MXFP4 quantisers and block-scaled MFMA GEMM op (``native/kernels/gemm_mxfp4.hip``,
+``native/kernels/quantize_mxfp4_tr.hip``).
 
 The format is OCP MX with e2m1 elements, blocks of 32 consecutive K elements
 and one E8M0 scale byte per block:
@@ -26,6 +27,12 @@ fp32 accumulation and bf16 output on ``v_mfma_scale_f32_32x32x64_f8f6f4``
 of every check: scaled block maxima land in [4, 8) and everything above 5
 becomes 6, so against the unquantised bf16 product the format's own error is
 about 21 % for uniform data.
+
+``quantize_mxfp4_t(x)`` and ``quantize_mxfp4_dual(x)`` give the images of the
+transposed tensor, whose blocks are 32 consecutive *rows* of ``x`` and whose
+bytes hold two row-neighbours, without a transposed copy: what the backward
+products of a linear layer contract over
+(``mxk8s.ops.linear.linear_mxfp4``).
 
 GPU tensors always run the hand-written kernels (no fallback); CPU tensors
 take the pure-torch reference path.
@@ -86,6 +93,47 @@ def quantize_mxfp4(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
                                        q.stride(0), s.stride(0), _lib.stream_ptr(x.device))
     _lib.check(st, "mxk_quantize_mxfp4")
     return q, s
+
+
+def quantize_mxfp4_t(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """bf16 ``[R, C]`` -> (packed e2m1 uint8 ``[C, R/2]``, uint8 E8M0 scales
+    ``[C, R/32]``): the images of ``quantize_mxfp4(x.t().contiguous())``, bit for
+    bit, from one pass over ``x``.  The MX blocks are 32 consecutive *rows* of
+    ``x`` (``R % 32 == 0``; any ``C``) and byte ``i`` of row ``c`` holds
+    ``x[2i, c]`` in bits 3:0 and ``x[2i+1, c]`` in bits 7:4, which is what a
+    product contracting over the row axis of ``x`` needs.  Finite inputs only.
+    A row stride larger than C is fine."""
+    _mx.check_xt(x, dual=False)
+    if x.device.type == "cpu":
+        return quantize_mxfp4_ref(x.t().contiguous())
+    R, C = x.shape
+    qt = torch.empty((C, R // 2), dtype=torch.uint8, device=x.device)
+    st = torch.empty((C, R // BLOCK), dtype=torch.uint8, device=x.device)
+    rc = _lib.lib().mxk_quantize_mxfp4_t(x.data_ptr(), qt.data_ptr(), st.data_ptr(), R, C,
+                                         x.stride(0), qt.stride(0), st.stride(0),
+                                         _lib.stream_ptr(x.device))
+    _lib.check(rc, "mxk_quantize_mxfp4_t")
+    return qt, st
+
+
+def quantize_mxfp4_dual(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor,
+                                                  torch.Tensor]:
+    """``(q, s, qt, st)``: ``quantize_mxfp4(x)`` and ``quantize_mxfp4_t(x)`` from
+    one read of ``x`` (bf16 ``[R, C]``, both multiples of 32)."""
+    _mx.check_xt(x, dual=True)
+    if x.device.type == "cpu":
+        return quantize_mxfp4_ref(x) + quantize_mxfp4_ref(x.t().contiguous())
+    R, C = x.shape
+    q = torch.empty((R, C // 2), dtype=torch.uint8, device=x.device)
+    s = torch.empty((R, C // BLOCK), dtype=torch.uint8, device=x.device)
+    qt = torch.empty((C, R // 2), dtype=torch.uint8, device=x.device)
+    st = torch.empty((C, R // BLOCK), dtype=torch.uint8, device=x.device)
+    rc = _lib.lib().mxk_quantize_mxfp4_dual(x.data_ptr(), q.data_ptr(), s.data_ptr(), qt.data_ptr(),
+                                            st.data_ptr(), R, C, x.stride(0), q.stride(0),
+                                            s.stride(0), qt.stride(0), st.stride(0),
+                                            _lib.stream_ptr(x.device))
+    _lib.check(rc, "mxk_quantize_mxfp4_dual")
+    return q, s, qt, st
 
 
 def _check_pair(q: torch.Tensor, s: torch.Tensor, qn: str, sn: str) -> None:

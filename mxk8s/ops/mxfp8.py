@@ -69,29 +69,13 @@ def quantize_mxfp8(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     return q, s
 
 
-def _check_xt(x: torch.Tensor, dual: bool) -> None:
-    if not isinstance(x, torch.Tensor):
-        raise TypeError("x must be a tensor")
-    if x.dtype != torch.bfloat16:
-        raise TypeError(f"x must be bfloat16, got {x.dtype}")
-    if x.dim() != 2:
-        raise ValueError(f"x must be 2-D, got shape {tuple(x.shape)}")
-    R, C = x.shape
-    if R == 0 or C == 0 or R % BLOCK or (dual and C % BLOCK):
-        raise ValueError(f"x must be [R, C] with R a positive multiple of {BLOCK} and C "
-                         + (f"a positive multiple of {BLOCK}" if dual else "> 0")
-                         + f", got {tuple(x.shape)}")
-    if x.stride(1) != 1:
-        raise ValueError("x must be row-major (stride(1) == 1)")
-
-
 def quantize_mxfp8_t(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     """bf16 ``[R, C]`` -> (e4m3 ``[C, R]``, uint8 E8M0 scales ``[C, R/32]``): the
     images of ``quantize_mxfp8(x.t().contiguous())``, bit for bit, from one pass
     over ``x``.  The MX blocks are 32 consecutive *rows* of ``x`` (``R % 32 ==
     0``; any ``C``), which is what a product contracting over the row axis of
     ``x`` needs.  Finite inputs only.  A row stride larger than C is fine."""
-    _check_xt(x, dual=False)
+    _mx.check_xt(x, dual=False)
     if x.device.type == "cpu":
         return quantize_mxfp8_ref(x.t().contiguous())
     R, C = x.shape
@@ -108,7 +92,7 @@ def quantize_mxfp8_dual(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor, to
                                                   torch.Tensor]:
     """``(q, s, qt, st)``: ``quantize_mxfp8(x)`` and ``quantize_mxfp8_t(x)`` from
     one read of ``x`` (bf16 ``[R, C]``, both multiples of 32)."""
-    _check_xt(x, dual=True)
+    _mx.check_xt(x, dual=True)
     if x.device.type == "cpu":
         return quantize_mxfp8_ref(x) + quantize_mxfp8_ref(x.t().contiguous())
     R, C = x.shape

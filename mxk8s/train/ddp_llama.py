@@ -59,13 +59,16 @@ def use_tuned_gemms(path: str = TUNED_GEMMS) -> bool:
     return bool(tunable.read_file(path))
 
 
+LINEAR_DTYPES = ("bf16", "mxfp8", "mxfp4")
+
+
 def resolve_linear_dtype(args) -> str:
     """``--linear-dtype``, else the environment variable ``MXK_LINEAR_DTYPE``
     (so ``bench.py --mode ddp`` can be A/B'd unchanged), else bf16.  An unknown
     value is an error."""
     v = getattr(args, "linear_dtype", None) or os.environ.get("MXK_LINEAR_DTYPE") or "bf16"
-    if v not in ("bf16", "mxfp8"):
-        raise ValueError(f"linear dtype must be bf16 or mxfp8, got {v!r}")
+    if v not in LINEAR_DTYPES:
+        raise ValueError(f"linear dtype must be one of {', '.join(LINEAR_DTYPES)}, got {v!r}")
     return v
 
 
@@ -310,9 +313,9 @@ def main(argv=None) -> int:
                    help="replicate the optimizer (all-reduce) instead of ZeRO-1 sharding")
     p.add_argument("--grad-reduce", choices=["bf16", "fp32"], default="bf16",
                    help="gradient wire format of the reduce-scatter / all-reduce")
-    p.add_argument("--linear-dtype", choices=["bf16", "mxfp8"], default=None,
-                   help="products of wqkv / wo / w13 / w2: bf16 kernels (default) or the MXFP8 "
-                        "GEMM; unset, the environment variable MXK_LINEAR_DTYPE decides")
+    p.add_argument("--linear-dtype", choices=list(LINEAR_DTYPES), default=None,
+                   help="products of wqkv / wo / w13 / w2: bf16 kernels (default), the MXFP8 or "
+                        "the MXFP4 GEMM; unset, the environment variable MXK_LINEAR_DTYPE decides")
     p.add_argument("--doc-len", type=int, default=None, metavar="MEAN",
                    help="pack each synthetic row with documents of this mean length and mask "
                         "attention at their boundaries; unset, the environment variable "
