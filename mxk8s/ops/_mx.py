@@ -52,6 +52,59 @@ def block_exponent(xb: torch.Tensor, emax: int) -> torch.Tensor:
     return torch.where(amax == 0, torch.zeros_like(e), e)
 
 
+def _images(x: torch.Tensor, per_byte: int, dtype: torch.dtype, transposed: bool):
+    """Uninitialised (codes, scales) of ``x`` ``[R, C]`` or of its transpose."""
+    R, C = x.shape[::-1] if transposed else x.shape
+    return (torch.empty((R, C // per_byte), dtype=dtype, device=x.device),
+            torch.empty((R, C // BLOCK), dtype=torch.uint8, device=x.device))
+
+
+def quantize_rows(name: str, per_byte: int, dtype: torch.dtype, ref: Callable, x: torch.Tensor):
+    """``quantize_<name>``: ``per_byte`` codes in each ``dtype`` item of ``q``,
+    ``ref`` the format's pure-torch quantiser, the kernel ``mxk_quantize_<name>``."""
+    check_x(x)
+    if x.device.type == "cpu":
+        return ref(x)
+    R, K = x.shape
+    q, s = _images(x, per_byte, dtype, False)
+    fn = f"mxk_quantize_{name}"
+    rc = getattr(_lib.lib(), fn)(x.data_ptr(), q.data_ptr(), s.data_ptr(), R, K, x.stride(0),
+                                 q.stride(0), s.stride(0), _lib.stream_ptr(x.device))
+    _lib.check(rc, fn)
+    return q, s
+
+
+def quantize_t(name: str, per_byte: int, dtype: torch.dtype, ref: Callable, x: torch.Tensor):
+    """``quantize_<name>_t``: the images of ``x.t()``; the kernel ``mxk_quantize_<name>_t``."""
+    check_xt(x, dual=False)
+    if x.device.type == "cpu":
+        return ref(x.t().contiguous())
+    R, C = x.shape
+    qt, st = _images(x, per_byte, dtype, True)
+    fn = f"mxk_quantize_{name}_t"
+    rc = getattr(_lib.lib(), fn)(x.data_ptr(), qt.data_ptr(), st.data_ptr(), R, C, x.stride(0),
+                                 qt.stride(0), st.stride(0), _lib.stream_ptr(x.device))
+    _lib.check(rc, fn)
+    return qt, st
+
+
+def quantize_dual(name: str, per_byte: int, dtype: torch.dtype, ref: Callable, x: torch.Tensor):
+    """``quantize_<name>_dual``: both images from one read of ``x``; the kernel
+    ``mxk_quantize_<name>_dual``."""
+    check_xt(x, dual=True)
+    if x.device.type == "cpu":
+        return ref(x) + ref(x.t().contiguous())
+    R, C = x.shape
+    q, s = _images(x, per_byte, dtype, False)
+    qt, st = _images(x, per_byte, dtype, True)
+    fn = f"mxk_quantize_{name}_dual"
+    rc = getattr(_lib.lib(), fn)(x.data_ptr(), q.data_ptr(), s.data_ptr(), qt.data_ptr(), st.data_ptr(),
+                                 R, C, x.stride(0), q.stride(0), s.stride(0), qt.stride(0),
+                                 st.stride(0), _lib.stream_ptr(x.device))
+    _lib.check(rc, fn)
+    return q, s, qt, st
+
+
 def check_pair(q: torch.Tensor, s: torch.Tensor, qn: str, sn: str, dtype: torch.dtype, wording: str,
                per_byte: int) -> None:
     """``q`` holds ``per_byte`` elements in each item of ``dtype``; ``wording``

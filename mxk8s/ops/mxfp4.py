@@ -1,5 +1,6 @@
-"""MXFP4 quantisers and block-scaled MFMA GEMM op (``native/kernels/gemm_mxfp4.hip``,
-``native/kernels/quantize_mxfp4_tr.hip``).
+"""MXFP4 quantisers and block-scaled MFMA GEMM op (``native/kernels/gemm_mxfp4.hip``;
+the quantiser kernels are the templates of ``native/kernels/mx_quantize.h``, shared
+with MXFP8).
 
 The format is OCP MX with e2m1 elements, blocks of 32 consecutive K elements
 and one E8M0 scale byte per block:
@@ -41,7 +42,7 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib, _mx
+from . import _mx
 from ._mx import BLOCK, TILE_M, TILE_N  # noqa: F401  (this module's constants, as before)
 
 E2M1_MAX = 6.0
@@ -83,16 +84,7 @@ def quantize_mxfp4_ref(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
 def quantize_mxfp4(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     """bf16 ``[R, K]`` -> (packed e2m1 uint8 ``[R, K/2]``, uint8 E8M0 scales
     ``[R, K/32]``).  Finite inputs only.  A row stride larger than K is fine."""
-    _mx.check_x(x)
-    if x.device.type == "cpu":
-        return quantize_mxfp4_ref(x)
-    R, K = x.shape
-    q = torch.empty((R, K // 2), dtype=torch.uint8, device=x.device)
-    s = torch.empty((R, K // BLOCK), dtype=torch.uint8, device=x.device)
-    st = _lib.lib().mxk_quantize_mxfp4(x.data_ptr(), q.data_ptr(), s.data_ptr(), R, K, x.stride(0),
-                                       q.stride(0), s.stride(0), _lib.stream_ptr(x.device))
-    _lib.check(st, "mxk_quantize_mxfp4")
-    return q, s
+    return _mx.quantize_rows("mxfp4", 2, torch.uint8, quantize_mxfp4_ref, x)
 
 
 def quantize_mxfp4_t(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
@@ -103,37 +95,14 @@ def quantize_mxfp4_t(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     ``x[2i, c]`` in bits 3:0 and ``x[2i+1, c]`` in bits 7:4, which is what a
     product contracting over the row axis of ``x`` needs.  Finite inputs only.
     A row stride larger than C is fine."""
-    _mx.check_xt(x, dual=False)
-    if x.device.type == "cpu":
-        return quantize_mxfp4_ref(x.t().contiguous())
-    R, C = x.shape
-    qt = torch.empty((C, R // 2), dtype=torch.uint8, device=x.device)
-    st = torch.empty((C, R // BLOCK), dtype=torch.uint8, device=x.device)
-    rc = _lib.lib().mxk_quantize_mxfp4_t(x.data_ptr(), qt.data_ptr(), st.data_ptr(), R, C,
-                                         x.stride(0), qt.stride(0), st.stride(0),
-                                         _lib.stream_ptr(x.device))
-    _lib.check(rc, "mxk_quantize_mxfp4_t")
-    return qt, st
+    return _mx.quantize_t("mxfp4", 2, torch.uint8, quantize_mxfp4_ref, x)
 
 
 def quantize_mxfp4_dual(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor,
                                                   torch.Tensor]:
     """``(q, s, qt, st)``: ``quantize_mxfp4(x)`` and ``quantize_mxfp4_t(x)`` from
     one read of ``x`` (bf16 ``[R, C]``, both multiples of 32)."""
-    _mx.check_xt(x, dual=True)
-    if x.device.type == "cpu":
-        return quantize_mxfp4_ref(x) + quantize_mxfp4_ref(x.t().contiguous())
-    R, C = x.shape
-    q = torch.empty((R, C // 2), dtype=torch.uint8, device=x.device)
-    s = torch.empty((R, C // BLOCK), dtype=torch.uint8, device=x.device)
-    qt = torch.empty((C, R // 2), dtype=torch.uint8, device=x.device)
-    st = torch.empty((C, R // BLOCK), dtype=torch.uint8, device=x.device)
-    rc = _lib.lib().mxk_quantize_mxfp4_dual(x.data_ptr(), q.data_ptr(), s.data_ptr(), qt.data_ptr(),
-                                            st.data_ptr(), R, C, x.stride(0), q.stride(0),
-                                            s.stride(0), qt.stride(0), st.stride(0),
-                                            _lib.stream_ptr(x.device))
-    _lib.check(rc, "mxk_quantize_mxfp4_dual")
-    return q, s, qt, st
+    return _mx.quantize_dual("mxfp4", 2, torch.uint8, quantize_mxfp4_ref, x)
 
 
 def _check_pair(q: torch.Tensor, s: torch.Tensor, qn: str, sn: str) -> None:

@@ -33,7 +33,7 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib, _mx
+from . import _mx
 from ._mx import BLOCK, TILE_M, TILE_N  # noqa: F401  (this module's constants, as before)
 
 E4M3_MAX = 448.0
@@ -57,16 +57,7 @@ def quantize_mxfp8_ref(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
 def quantize_mxfp8(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     """bf16 ``[R, K]`` -> (e4m3 ``[R, K]``, uint8 E8M0 scales ``[R, K/32]``).
     Finite inputs only.  A row stride larger than K is fine."""
-    _mx.check_x(x)
-    if x.device.type == "cpu":
-        return quantize_mxfp8_ref(x)
-    R, K = x.shape
-    q = torch.empty((R, K), dtype=torch.float8_e4m3fn, device=x.device)
-    s = torch.empty((R, K // BLOCK), dtype=torch.uint8, device=x.device)
-    st = _lib.lib().mxk_quantize_mxfp8(x.data_ptr(), q.data_ptr(), s.data_ptr(), R, K, x.stride(0),
-                                       q.stride(0), s.stride(0), _lib.stream_ptr(x.device))
-    _lib.check(st, "mxk_quantize_mxfp8")
-    return q, s
+    return _mx.quantize_rows("mxfp8", 1, torch.float8_e4m3fn, quantize_mxfp8_ref, x)
 
 
 def quantize_mxfp8_t(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
@@ -75,37 +66,14 @@ def quantize_mxfp8_t(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     over ``x``.  The MX blocks are 32 consecutive *rows* of ``x`` (``R % 32 ==
     0``; any ``C``), which is what a product contracting over the row axis of
     ``x`` needs.  Finite inputs only.  A row stride larger than C is fine."""
-    _mx.check_xt(x, dual=False)
-    if x.device.type == "cpu":
-        return quantize_mxfp8_ref(x.t().contiguous())
-    R, C = x.shape
-    qt = torch.empty((C, R), dtype=torch.float8_e4m3fn, device=x.device)
-    st = torch.empty((C, R // BLOCK), dtype=torch.uint8, device=x.device)
-    rc = _lib.lib().mxk_quantize_mxfp8_t(x.data_ptr(), qt.data_ptr(), st.data_ptr(), R, C,
-                                         x.stride(0), qt.stride(0), st.stride(0),
-                                         _lib.stream_ptr(x.device))
-    _lib.check(rc, "mxk_quantize_mxfp8_t")
-    return qt, st
+    return _mx.quantize_t("mxfp8", 1, torch.float8_e4m3fn, quantize_mxfp8_ref, x)
 
 
 def quantize_mxfp8_dual(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor,
                                                   torch.Tensor]:
     """``(q, s, qt, st)``: ``quantize_mxfp8(x)`` and ``quantize_mxfp8_t(x)`` from
     one read of ``x`` (bf16 ``[R, C]``, both multiples of 32)."""
-    _mx.check_xt(x, dual=True)
-    if x.device.type == "cpu":
-        return quantize_mxfp8_ref(x) + quantize_mxfp8_ref(x.t().contiguous())
-    R, C = x.shape
-    q = torch.empty((R, C), dtype=torch.float8_e4m3fn, device=x.device)
-    s = torch.empty((R, C // BLOCK), dtype=torch.uint8, device=x.device)
-    qt = torch.empty((C, R), dtype=torch.float8_e4m3fn, device=x.device)
-    st = torch.empty((C, R // BLOCK), dtype=torch.uint8, device=x.device)
-    rc = _lib.lib().mxk_quantize_mxfp8_dual(x.data_ptr(), q.data_ptr(), s.data_ptr(), qt.data_ptr(),
-                                            st.data_ptr(), R, C, x.stride(0), q.stride(0),
-                                            s.stride(0), qt.stride(0), st.stride(0),
-                                            _lib.stream_ptr(x.device))
-    _lib.check(rc, "mxk_quantize_mxfp8_dual")
-    return q, s, qt, st
+    return _mx.quantize_dual("mxfp8", 1, torch.float8_e4m3fn, quantize_mxfp8_ref, x)
 
 
 def _check_pair(q: torch.Tensor, s: torch.Tensor, qn: str, sn: str) -> None:

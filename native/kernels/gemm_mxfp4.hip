@@ -2,12 +2,15 @@
 // and block-scaled MFMA GEMM for gfx950.
 //
 //   mxk_quantize_mxfp4   bf16 rows -> packed e2m1 nibbles + E8M0 scale bytes
+//   mxk_quantize_mxfp4_t     the same of x^T (blocks of 32 rows), stored transposed
+//   mxk_quantize_mxfp4_dual  both images from one read of x
 //   mxk_gemm_mxfp4_tn    C[M][N] = dequant(A) . dequant(B)^T, fp32
 //                        accumulation, bf16 output; both operands K-contiguous
 //
 // Storage (mxfp4_format.h has the arithmetic): element 2 i of a row sits in
 // bits 3:0 of byte i, element 2 i + 1 in bits 7:4; row strides of the packed
-// elements (lda, ldb, ldq) count bytes.
+// elements (lda, ldb, ldq, ldqt) count bytes.  So byte i of row c of qt holds
+// x[2 i][c] in bits 3:0 and x[2 i + 1][c] in bits 7:4.
 //
 // ---- operand and scale lane map of v_mfma_scale_f32_32x32x64_f8f6f4 --------
 // (cbsz = blgp = 4: both operands e2m1, 4 VGPRs each; established with a
@@ -39,10 +42,10 @@
 // K-tile of 256 elements = 128 B per row, LDS image (LDS-DMA, 16-B chunks
 // XOR-swizzled by (row >> 1) & 7), two stages, one barrier per K-tile.  That
 // header holds the staging (LDS-DMA descriptor), barrier and epilogue-store
-// helpers, the validation and launch of the entry points and the quantiser's
-// quarter-block routine, once for both formats; this file keeps the format,
-// the kernel with its K-tile, MFMA, fragment and scale helpers, and the entry
-// points.  A K-tile is four MFMA
+// helpers and the validation and launch of the GEMM entry point, and
+// mx_quantize.h the quantiser kernels as templates on the format, once for
+// both formats; this file keeps the format, the kernel with its K-tile, MFMA,
+// fragment and scale helpers, and the entry points.  A K-tile is four MFMA
 // k-steps of 64; each costs half the matrix-core time of an e4m3 k-step, so
 // they are issued in pairs and a pair stands where the MXFP8 kernel has one
 // k-step:
@@ -57,6 +60,7 @@
 // the tile.  Two 68 KiB stages.  The MFMAs are the compiler builtin: it places
 // the hazard waits and the accumulators.
 #include "mx_gemm_core.h"
+#include "mx_quantize.h"
 #include "mxfp4_format.h"
 
 namespace {
@@ -66,8 +70,8 @@ using namespace mxk::mx;
 // ---------------------------------------------------------------------------
 // Quantiser
 // ---------------------------------------------------------------------------
-// The element format of the shared quantiser (mx_gemm_core.h): one packed
-// dword per lane.
+// The element format of the shared quantiser kernels (mx_quantize.h): one
+// packed dword per lane.
 struct E2m1 {
   static constexpr int kBits = 4;
   static constexpr float kMax = mxfp4::kMax;
@@ -75,41 +79,6 @@ struct E2m1 {
   __device__ static float inv_scale(int e) { return mxfp4::block_inv_scale(e); }
   __device__ static uint32_t convert(float v) { return mxfp4::f32_to_e2m1(v); }
 };
-
-// One lane per 8 consecutive elements (one packed dword), 4 lanes (a DPP quad)
-// per MX block.  The body is its own copy in either format's file: written
-// once as a function that both kernels call, it compiles to other by-element
-// kernels.
-template <bool VEC>
-__global__ void __launch_bounds__(256)
-quantize_mxfp4_kernel(const uint16_t* __restrict__ x, uint8_t* __restrict__ q,
-                      uint8_t* __restrict__ s, long R, int K, long ldx, long ldq, long lds) {
-  const long per_row = K >> 3;
-  const long gid = static_cast<long>(blockIdx.x) * blockDim.x + threadIdx.x;
-  // K % 32 == 0, so a quad never straddles a row and leaves the grid whole
-  if (gid >= R * per_row) return;
-  const long row = gid / per_row;
-  const int c8 = static_cast<int>(gid - row * per_row);
-  const uint16_t* xp = x + row * ldx + c8 * 8;
-  uint32_t w[4];
-  if constexpr (VEC) {
-    const uint4 v = *reinterpret_cast<const uint4*>(xp);
-    w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-  } else {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) w[i] = xp[2 * i] | (static_cast<uint32_t>(xp[2 * i + 1]) << 16);
-  }
-  uint32_t out[1];
-  const int e = quantize_quarter<E2m1>(w, out);
-  uint8_t* qp = q + row * ldq + c8 * 4;
-  if constexpr (VEC) {
-    store_quarter<E2m1>(qp, out);
-  } else {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) qp[i] = static_cast<uint8_t>(out[i >> 2] >> (8 * (i & 3)));
-  }
-  if ((c8 & 3) == 0) s[row * lds + (c8 >> 2)] = static_cast<uint8_t>(e + 127);
-}
 
 // ---------------------------------------------------------------------------
 // GEMM
@@ -348,6 +317,23 @@ MXK_API int mxk_gemm_mxfp4_tn(const void* Aq, const void* As, const void* Bq, co
 // [R][K / 32] (row stride lds).  The definition is in mxfp4_format.h.
 MXK_API int mxk_quantize_mxfp4(const void* x, void* q, void* s, long R, int K, long ldx, long ldq,
                                long lds, hipStream_t stream) {
-  return launch_quantize_rows<E2m1>(quantize_mxfp4_kernel<true>, quantize_mxfp4_kernel<false>, x, q, s,
-                                    R, K, ldx, ldq, lds, stream);
+  return launch_quantize_rows<E2m1>(x, q, s, R, K, ldx, ldq, lds, stream);
+}
+
+// x: bf16 [R][C] (row stride ldx elements), R % 32 == 0, any C > 0, finite
+// values only.  qt: packed e2m1 [C][R / 2] bytes (row stride ldqt bytes), st:
+// E8M0 bytes [C][R / 32] (row stride ldst): mxk_quantize_mxfp4 of x^T, bit for
+// bit, the MX blocks being 32 consecutive rows of x.  Nothing outside the
+// [C][R / 2] and [C][R / 32] extents is written.
+MXK_API int mxk_quantize_mxfp4_t(const void* x, void* qt, void* st, long R, long C, long ldx,
+                                 long ldqt, long ldst, hipStream_t stream) {
+  return launch_quantize_tr<E2m1>(false, x, nullptr, nullptr, qt, st, R, C, ldx, 0, 0, ldqt, ldst, stream);
+}
+
+// q / s: the image mxk_quantize_mxfp4 writes ([R][C / 2] and [R][C / 32]; C %
+// 32 == 0 as well); qt / st: that of mxk_quantize_mxfp4_t; x is read once.
+MXK_API int mxk_quantize_mxfp4_dual(const void* x, void* q, void* s, void* qt, void* st, long R,
+                                    long C, long ldx, long ldq, long lds, long ldqt, long ldst,
+                                    hipStream_t stream) {
+  return launch_quantize_tr<E2m1>(true, x, q, s, qt, st, R, C, ldx, ldq, lds, ldqt, ldst, stream);
 }

@@ -27,6 +27,8 @@
 // lane index is the row of C and each lane owns runs of 4 consecutive columns.
 //
 // ---- structure --------------------------------------------------------------
+// The quantiser kernels are mx_quantize.h's templates on struct E4m3, which the
+// MXFP4 file shares.  The GEMM:
 // 256x256 output tile, 4 waves (2 x 2, 128x128 each = 4 x 4 MFMA blocks), K-tile
 // of 128 elements = 128 B per row = two MFMA k-steps.  A K-tile costs the same
 // matrix-core time and stages the same bytes as a bf16 K-tile of 64
@@ -41,6 +43,7 @@
 // so a stage has one whole K-tile to land.  The MFMAs are the compiler
 // builtin: it places the hazard waits and the accumulators.
 #include "mx_gemm_core.h"
+#include "mx_quantize.h"
 
 namespace {
 
@@ -49,7 +52,7 @@ using namespace mxk::mx;
 // ---------------------------------------------------------------------------
 // Quantiser
 // ---------------------------------------------------------------------------
-// The element format of the shared quantiser (mx_gemm_core.h).
+// The element format of the shared quantiser kernels (mx_quantize.h).
 struct E4m3 {
   static constexpr int kBits = 8;
   static constexpr float kMax = 448.f;
@@ -88,145 +91,6 @@ struct E4m3 {
     return r | sign;
   }
 };
-
-// One lane per 8 consecutive elements, 4 lanes (a DPP quad) per MX
-// block.  The body is its own copy in either format's file: written once as a
-// function that both kernels call, it compiles to other by-element kernels.
-template <bool VEC>
-__global__ void __launch_bounds__(256)
-quantize_mxfp8_kernel(const uint16_t* __restrict__ x, uint8_t* __restrict__ q,
-                      uint8_t* __restrict__ s, long R, int K, long ldx, long ldq, long lds) {
-  const long per_row = K >> 3;
-  const long gid = static_cast<long>(blockIdx.x) * blockDim.x + threadIdx.x;
-  // K % 32 == 0, so a quad never straddles a row and leaves the grid whole
-  if (gid >= R * per_row) return;
-  const long row = gid / per_row;
-  const int c8 = static_cast<int>(gid - row * per_row);
-  const uint16_t* xp = x + row * ldx + c8 * 8;
-  uint32_t w[4];
-  if constexpr (VEC) {
-    const uint4 v = *reinterpret_cast<const uint4*>(xp);
-    w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-  } else {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) w[i] = xp[2 * i] | (static_cast<uint32_t>(xp[2 * i + 1]) << 16);
-  }
-  uint32_t out[2];
-  const int e = quantize_quarter<E4m3>(w, out);
-  uint8_t* qp = q + row * ldq + c8 * 8;
-  if constexpr (VEC) {
-    store_quarter<E4m3>(qp, out);
-  } else {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) qp[i] = static_cast<uint8_t>(out[i >> 2] >> (8 * (i & 3)));
-  }
-  if ((c8 & 3) == 0) s[row * lds + (c8 >> 2)] = static_cast<uint8_t>(e + 127);
-}
-
-// ---- transposing quantiser ----------------------------------------------------
-// qt[c][r], st[c][r / 32]: the MX blocks are 32 consecutive ROWS of x.  A
-// workgroup takes a 128-row x 64-column tile of x:
-//   load   lane = (row pair, 8-column chunk): two 16-B row accesses (rows r and
-//          r + 1), per wave instruction 8 row pairs x 128 B.  DUAL: the two
-//          rows are also quantised along the row (the chunks of a 32-column
-//          block sit in one DPP quad) and stored, the image of
-//          quantize_mxfp8_kernel.
-//   LDS    transposed image T[c][r] of bf16: x[r][c], x[r + 1][c] go out as one
-//          dword.  A T row is 256 B + 8 B of padding (66 dwords).  A 32-lane
-//          store group holds chunks k = 0..3 (or 4..7) of 8 row pairs: dword
-//          bank (mod 32) 16 (k & 1) + 2 j + pair, 2-way, which a 4-B LDS store
-//          hides.  Unpadded, the 8 (or 4) chunks of a group would meet on one
-//          bank per row pair.  A column read is 16 B per lane at an 8-B aligned
-//          address (one ds_read2_b64): 16 lanes read 256 contiguous bytes of
-//          one T row, 2-way on the 32 banks that instruction has; 4 reads per
-//          lane against 16 stored dwords.
-//   store  lane = (column, 8 rows): amax over the quad that shares the block,
-//          8 contiguous bytes of qt per lane, 128 B per column and tile.
-// Rows >= R and columns >= C of a ragged tile load zeros and store nothing.
-constexpr int kTrRows = 128, kTrCols = 64;
-constexpr int kTrLdsRow = kTrRows * 2 + 8;   // bytes
-
-template <bool VEC, bool DUAL>
-__global__ void __launch_bounds__(256)
-quantize_mxfp8_tr_kernel(const uint16_t* __restrict__ x, uint8_t* __restrict__ q,
-                         uint8_t* __restrict__ s, uint8_t* __restrict__ qt, uint8_t* __restrict__ st,
-                         long R, long C, long ldx, long ldq, long lds, long ldqt, long ldst) {
-  __shared__ __attribute__((aligned(8))) char tile[kTrCols * kTrLdsRow];
-  const int t = threadIdx.x;
-  const int lane = t & 63, wave = t >> 6;
-  const long r0 = static_cast<long>(blockIdx.x) * kTrRows;
-  const long c0 = static_cast<long>(blockIdx.y) * kTrCols;
-  const int k = (lane & 3) | ((lane >> 5) << 2);   // 8-column chunk
-  const int pair = (lane >> 2) & 7;
-  const long col = c0 + k * 8;
-#pragma unroll
-  for (int pass = 0; pass < 2; ++pass) {
-    const int rl = pass * 64 + wave * 16 + pair * 2;   // even row inside the tile
-    uint32_t w[2][4];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const long row = r0 + rl + h;
-      const uint16_t* xp = x + row * ldx + col;
-      if constexpr (VEC) {
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (row < R && col < C) v = *reinterpret_cast<const uint4*>(xp);   // C % 8 == 0
-        w[h][0] = v.x; w[h][1] = v.y; w[h][2] = v.z; w[h][3] = v.w;
-      } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const uint32_t lo = (row < R && col + 2 * i < C) ? xp[2 * i] : 0u;
-          const uint32_t hi = (row < R && col + 2 * i + 1 < C) ? xp[2 * i + 1] : 0u;
-          w[h][i] = lo | (hi << 16);
-        }
-      }
-      if constexpr (DUAL) {
-        uint32_t out[2];
-        const int e = quantize_quarter<E4m3>(w[h], out);
-        if (row < R && col < C) {   // C % 32 == 0: whole blocks
-          uint8_t* qp = q + row * ldq + col;
-          if constexpr (VEC) {
-            store_quarter<E4m3>(qp, out);
-          } else {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) qp[i] = static_cast<uint8_t>(out[i >> 2] >> (8 * (i & 3)));
-          }
-          if ((k & 3) == 0) s[row * lds + (col >> 5)] = static_cast<uint8_t>(e + 127);
-        }
-      }
-    }
-    char* tp = tile + (k * 8) * kTrLdsRow + rl * 2;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      *reinterpret_cast<uint32_t*>(tp + (2 * i) * kTrLdsRow) = (w[0][i] & 0xFFFFu) | (w[1][i] << 16);
-      *reinterpret_cast<uint32_t*>(tp + (2 * i + 1) * kTrLdsRow) =
-          (w[0][i] >> 16) | (w[1][i] & 0xFFFF0000u);
-    }
-  }
-  __syncthreads();
-  const int r8 = t & 15;
-  const long row = r0 + r8 * 8;
-#pragma unroll
-  for (int pass = 0; pass < 4; ++pass) {
-    const int cl = pass * 16 + (t >> 4);
-    const char* tp = tile + cl * kTrLdsRow + r8 * 16;
-    const uint2 a = *reinterpret_cast<const uint2*>(tp);
-    const uint2 b = *reinterpret_cast<const uint2*>(tp + 8);
-    const uint32_t w[4] = {a.x, a.y, b.x, b.y};
-    uint32_t out[2];
-    const int e = quantize_quarter<E4m3>(w, out);
-    const long c = c0 + cl;
-    if (row < R && c < C) {   // R % 32 == 0: whole blocks
-      uint8_t* qp = qt + c * ldqt + row;
-      if constexpr (VEC) {
-        store_quarter<E4m3>(qp, out);
-      } else {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) qp[i] = static_cast<uint8_t>(out[i >> 2] >> (8 * (i & 3)));
-      }
-      if ((r8 & 3) == 0) st[c * ldst + (row >> 5)] = static_cast<uint8_t>(e + 127);
-    }
-  }
-}
 
 // ---------------------------------------------------------------------------
 // GEMM
@@ -443,40 +307,8 @@ MXK_API int mxk_gemm_mxfp8_tn(const void* Aq, const void* As, const void* Bq, co
 // byte e + 127 (127 for a zero block), element RNE(clamp(x 2^-e, +-448)).
 MXK_API int mxk_quantize_mxfp8(const void* x, void* q, void* s, long R, int K, long ldx, long ldq,
                                long lds, hipStream_t stream) {
-  return launch_quantize_rows<E4m3>(quantize_mxfp8_kernel<true>, quantize_mxfp8_kernel<false>, x, q, s,
-                                    R, K, ldx, ldq, lds, stream);
+  return launch_quantize_rows<E4m3>(x, q, s, R, K, ldx, ldq, lds, stream);
 }
-
-namespace {
-
-int launch_quantize_tr(bool dual, const void* x, void* q, void* s, void* qt, void* st, long R, long C,
-                       long ldx, long ldq, long lds, long ldqt, long ldst, hipStream_t stream) {
-  if (!x || !qt || !st || R <= 0 || C <= 0 || R % 32 || ldx < C || ldqt < R || ldst < R / 32)
-    return static_cast<int>(hipErrorInvalidValue);
-  if (dual && (!q || !s || C % 32 || ldq < C || lds < C / 32))
-    return static_cast<int>(hipErrorInvalidValue);
-  const long gx = (R + kTrRows - 1) / kTrRows, gy = (C + kTrCols - 1) / kTrCols;
-  if (gx > 0x7FFFFFFFL || gy > 65535) return static_cast<int>(hipErrorInvalidValue);
-  // 16-B row accesses of x, 8-B stores of qt (and q): everything else goes by element
-  const bool vec = aligned(x, 16) && ldx % 8 == 0 && C % 8 == 0 && aligned(qt, 8) && ldqt % 8 == 0 &&
-                   (!dual || (aligned(q, 8) && ldq % 8 == 0));
-  const dim3 grid(static_cast<unsigned>(gx), static_cast<unsigned>(gy));
-  auto go = [&](auto kernel) {
-    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, static_cast<const uint16_t*>(x),
-                       static_cast<uint8_t*>(q), static_cast<uint8_t*>(s), static_cast<uint8_t*>(qt),
-                       static_cast<uint8_t*>(st), R, C, ldx, ldq, lds, ldqt, ldst);
-  };
-  if (dual) {
-    if (vec) go(quantize_mxfp8_tr_kernel<true, true>);
-    else go(quantize_mxfp8_tr_kernel<false, true>);
-  } else {
-    if (vec) go(quantize_mxfp8_tr_kernel<true, false>);
-    else go(quantize_mxfp8_tr_kernel<false, false>);
-  }
-  MXK_RETURN_LAUNCH_STATUS();
-}
-
-}  // namespace
 
 // x: bf16 [R][C] (row stride ldx elements), R % 32 == 0, finite values only.
 // qt: e4m3 bytes [C][R] (row stride ldqt), st: E8M0 bytes [C][R / 32] (row
@@ -484,7 +316,7 @@ int launch_quantize_tr(bool dual, const void* x, void* q, void* s, void* qt, voi
 // rows of x.  Nothing outside the [C][R] and [C][R / 32] extents is written.
 MXK_API int mxk_quantize_mxfp8_t(const void* x, void* qt, void* st, long R, long C, long ldx,
                                  long ldqt, long ldst, hipStream_t stream) {
-  return launch_quantize_tr(false, x, nullptr, nullptr, qt, st, R, C, ldx, 0, 0, ldqt, ldst, stream);
+  return launch_quantize_tr<E4m3>(false, x, nullptr, nullptr, qt, st, R, C, ldx, 0, 0, ldqt, ldst, stream);
 }
 
 // q / s: the image mxk_quantize_mxfp8 writes (C % 32 == 0 as well); qt / st:
@@ -492,5 +324,5 @@ MXK_API int mxk_quantize_mxfp8_t(const void* x, void* qt, void* st, long R, long
 MXK_API int mxk_quantize_mxfp8_dual(const void* x, void* q, void* s, void* qt, void* st, long R,
                                     long C, long ldx, long ldq, long lds, long ldqt, long ldst,
                                     hipStream_t stream) {
-  return launch_quantize_tr(true, x, q, s, qt, st, R, C, ldx, ldq, lds, ldqt, ldst, stream);
+  return launch_quantize_tr<E4m3>(true, x, q, s, qt, st, R, C, ldx, ldq, lds, ldqt, ldst, stream);
 }

@@ -1,8 +1,8 @@
-// What the block-scaled (OCP MX) GEMMs and quantisers share, written once: the
-// staging, barrier and epilogue-store helpers, the quantiser's quarter-block
-// routine and the host sides of the entry points.  gemm_mxfp8.hip (e4m3) and
-// gemm_mxfp4.hip (e2m1) keep their format, their kernels and the lane maps of
-// their MFMA operands.
+// What the block-scaled (OCP MX) GEMMs share, written once: the staging,
+// barrier and epilogue-store helpers and the host side of the entry points.
+// gemm_mxfp8.hip (e4m3) and gemm_mxfp4.hip (e2m1) keep their format, their
+// kernels and the lane maps of their MFMA operands; the quantisers of both are
+// in mx_quantize.h.
 //
 // Shared tile: 256x256 output, 4 waves (2 x 2, 128x128 each = 4 x 4 MFMA
 // blocks of 32x32), K-tile rows of 128 B whatever the element width, LDS image
@@ -15,9 +15,11 @@
 // across a function boundary can move instructions: scripts/isa_stream.py
 // compares the streams.  With what is here, every kernel of the two files has
 // the instruction stream it had with its own copy of each helper.  The two GEMM
-// kernel bodies (prologue, K loops, epilogue) and the row quantiser kernels
-// stay in the formats' files: as one function called from both files they
-// compile to other streams (profiles/mx_gemm_core/).
+// kernel bodies (prologue, K loops, epilogue) stay in the formats' files: as
+// one function called from both files they compile to other streams
+// (profiles/mx_gemm_core/).  A kernel template does not have that problem,
+// each instantiation being the code a copy would be: the quantiser kernels are
+// written that way (mx_quantize.h, profiles/mx_quantize/).
 #pragma once
 #include "mx_common.h"
 
@@ -34,75 +36,7 @@ constexpr int kThreads = 256;
 constexpr int kOpBytes = 256 * kRowBytes;        // 32 KiB per operand per stage
 constexpr int kScaleOff = 2 * kOpBytes;          // the scale planes (1 KiB each)
 
-// ---------------------------------------------------------------------------
-// Quantiser.  Fmt: kBits per element, kMax (saturation bound),
-// block_exp(amax), inv_scale(e) = 2^-e, convert(v) = the element's code.
-// ---------------------------------------------------------------------------
-// 8 consecutive elements of an MX block (4 dwords of two bf16 each, memory
-// order) whose other 24 are in the lane's DPP quad: the 8 codes packed in
-// memory order; returns the block's exponent.  Every lane of the quad must be
-// active.
-template <class Fmt>
-__device__ __forceinline__ int quantize_quarter(const uint32_t (&w)[4],
-                                                uint32_t (&out)[Fmt::kBits / 4]) {
-  float f[8];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    f[2 * i] = __uint_as_float(w[i] << 16);
-    f[2 * i + 1] = __uint_as_float(w[i] & 0xFFFF0000u);
-  }
-  float amax = 0.f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) amax = fmaxf(amax, fabsf(f[i]));
-  // the block's other three lanes: quad_perm [1,0,3,2] then [2,3,0,1]
-  amax = fmaxf(amax, __uint_as_float(__builtin_amdgcn_mov_dpp(__float_as_uint(amax), 0xB1, 0xF, 0xF, true)));
-  amax = fmaxf(amax, __uint_as_float(__builtin_amdgcn_mov_dpp(__float_as_uint(amax), 0x4E, 0xF, 0xF, true)));
-  const int e = Fmt::block_exp(amax);
-  const float inv = Fmt::inv_scale(e);
-#pragma unroll
-  for (int i = 0; i < Fmt::kBits / 4; ++i) out[i] = 0;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const float v = fminf(fmaxf(f[i] * inv, -Fmt::kMax), Fmt::kMax);   // explicit saturation
-    out[i * Fmt::kBits / 32] |= Fmt::convert(v) << (i * Fmt::kBits % 32);
-  }
-  return e;
-}
-
-// The packed codes of quantize_quarter to an aligned qp: one 8-B (e4m3) or 4-B
-// (e2m1) store.  The by-byte form for an unaligned qp,
-//   for (i < Fmt::kBits) qp[i] = out[i >> 2] >> (8 * (i & 3)),
-// stays inline in the quantiser kernels, and so do the row kernels' bodies.
-template <class Fmt>
-__device__ __forceinline__ void store_quarter(uint8_t* qp, const uint32_t (&out)[Fmt::kBits / 4]) {
-  if constexpr (Fmt::kBits == 8) *reinterpret_cast<uint2*>(qp) = make_uint2(out[0], out[1]);
-  else *reinterpret_cast<uint32_t*>(qp) = out[0];
-}
-
 inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
-// Host side of a row quantiser: x bf16 [R][K] (row stride ldx elements), K %
-// 32 == 0; q packed codes (row stride ldq bytes); s E8M0 bytes [R][K / 32].
-// vec_kernel / elem_kernel: the format's row kernel with 16-B loads and one
-// packed store per lane / going by element.
-using QuantizeRowsKernel = void (*)(const uint16_t*, uint8_t*, uint8_t*, long, int, long, long, long);
-template <class Fmt>
-int launch_quantize_rows(QuantizeRowsKernel vec_kernel, QuantizeRowsKernel elem_kernel, const void* x,
-                         void* q, void* s, long R, int K, long ldx, long ldq, long lds,
-                         hipStream_t stream) {
-  if (!x || !q || !s || R <= 0 || K <= 0 || K % 32 || ldx < K || ldq < K * Fmt::kBits / 8 ||
-      lds < K / 32)
-    return static_cast<int>(hipErrorInvalidValue);
-  const long lanes = R * (K / 8);
-  const long blocks = (lanes + 255) / 256;
-  if (blocks > 0x7FFFFFFFL) return static_cast<int>(hipErrorInvalidValue);
-  // 16-B loads of x, kBits-byte stores of q: everything else goes by element
-  const bool vec = aligned(x, 16) && ldx % 8 == 0 && aligned(q, Fmt::kBits) && ldq % Fmt::kBits == 0;
-  hipLaunchKernelGGL(vec ? vec_kernel : elem_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0,
-                     stream, static_cast<const uint16_t*>(x), static_cast<uint8_t*>(q),
-                     static_cast<uint8_t*>(s), R, K, ldx, ldq, lds);
-  MXK_RETURN_LAUNCH_STATUS();
-}
 
 // ---------------------------------------------------------------------------
 // GEMM helpers

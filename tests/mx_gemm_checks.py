@@ -4,9 +4,13 @@ format and the check bodies written once against it.  The shapes and
 parametrisations stay in the test files; they differ per format on purpose
 (K-tile 128 against 256).  A plain helper module, not collected.
 """
+import functools
 import os
+import re
+import shutil
 import stat
 import subprocess
+import tempfile
 from dataclasses import dataclass
 from typing import Callable
 
@@ -17,6 +21,8 @@ from mxk8s import ops
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.environ.get("MXK8S_BIN", os.path.join(REPO, "bin"))
+_HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+HIPCC = _HIPCC if os.path.exists(_HIPCC) else shutil.which("hipcc")    # None: no compiler
 
 
 def _one_hot_scales(rows, K):
@@ -51,6 +57,7 @@ def _one_hot_mxfp4(rows, K, mult, off, code_mul, code_off, neg_every):
 @dataclass(frozen=True)
 class Format:
     name: str
+    struct: str              # the element format's struct in the quantiser kernels' symbols
     quantize: Callable
     quantize_ref: Callable
     dequantize: Callable
@@ -74,10 +81,46 @@ class Format:
         return "mxk_gemm_%s_tn" % self.name
 
 
-MXFP8 = Format("mxfp8", ops.quantize_mxfp8, ops.quantize_mxfp8_ref, ops.dequantize_mxfp8,
+MXFP8 = Format("mxfp8", "E4m3", ops.quantize_mxfp8, ops.quantize_mxfp8_ref, ops.dequantize_mxfp8,
                ops.gemm_mxfp8_tn, torch.float8_e4m3fn, 1, 128, _one_hot_mxfp8, 0x7f, 64)
-MXFP4 = Format("mxfp4", ops.quantize_mxfp4, ops.quantize_mxfp4_ref, ops.dequantize_mxfp4,
+MXFP4 = Format("mxfp4", "E2m1", ops.quantize_mxfp4, ops.quantize_mxfp4_ref, ops.dequantize_mxfp4,
                ops.gemm_mxfp4_tn, torch.uint8, 2, 256, _one_hot_mxfp4, 0xFF, 128)
+
+
+# ---- build hygiene ---------------------------------------------------------------
+_META = ("private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count")
+
+
+@functools.lru_cache(maxsize=None)
+def kernel_listing(f):
+    """native/kernels/gemm_<name>.hip compiled for gfx950, device only: the
+    assembly and, per kernel symbol, its scratch size and spill counts."""
+    with tempfile.TemporaryDirectory() as tmp:
+        out = os.path.join(tmp, "m.s")
+        subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17",
+                        "-I" + os.path.join(REPO, "native", "kernels"), "--cuda-device-only", "-S",
+                        os.path.join(REPO, "native", "kernels", "gemm_%s.hip" % f.name), "-o", out],
+                       check=True, capture_output=True)
+        with open(out) as fh:
+            asm = fh.read()
+    by = {}
+    kernels = asm[asm.index("amdhsa.kernels:"):]
+    for entry in kernels[:kernels.index("\namdhsa.")].split("\n  - ")[1:]:
+        name = re.search(r"\n    \.name:\s+(\S+)", entry).group(1)    # at the entry's own depth
+        by[name] = {k: int(re.search(r"\n    \.%s:\s+(\d+)" % k, entry).group(1)) for k in _META}
+    return asm, by
+
+
+def check_quantiser_kernels(f, by, kernel, count):
+    """Exactly `count` instantiations of the shared quantiser `kernel` on this
+    format's struct and none on another; each without scratch or spills: all
+    3 x count metadata fields are there and zero.  Returns their symbols."""
+    named = [n for n in by if kernel in n]
+    mine = [n for n in named if f.struct in n]
+    assert len(mine) == count and named == mine, sorted(by)
+    fields = [(n, k, by[n][k]) for n in mine for k in _META]
+    assert len(fields) == 3 * count and all(v == 0 for _, _, v in fields), fields
+    return mine
 
 
 # ---- GPU checks -----------------------------------------------------------------

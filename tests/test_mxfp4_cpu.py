@@ -3,12 +3,12 @@ quantiser, the op's contract, validator plumbing, build hygiene of
 ``native/kernels/gemm_mxfp4.hip`` and the host sweep of ``mxfp4_format.h``."""
 import os
 import re
-import shutil
 import subprocess
 
 import pytest
 import torch
 
+import mx_gemm_checks as mx
 import mxk8s.validate.__main__ as V
 from mx_gemm_checks import fake_bench, run_validator
 from mxk8s.ops import _lib
@@ -16,7 +16,6 @@ from mxk8s.ops.mxfp4 import (dequantize_mxfp4, gemm_mxfp4_tn, is_fast_shape_mxfp
                              quantize_mxfp4_ref)
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 MAGNITUDES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
 
 
@@ -324,28 +323,17 @@ def test_validator_still_rejects_fp4_without_the_mx_prefix(capsys):
 
 
 # ---- build hygiene ----------------------------------------------------------------
-@pytest.mark.skipif(not os.path.exists(HIPCC) and not shutil.which("hipcc"), reason="no hipcc")
-def test_gemm_kernel_has_no_scratch_and_uses_the_scaled_mfma_on_e2m1(tmp_path):
-    out = str(tmp_path / "m.s")
-    subprocess.run([HIPCC if os.path.exists(HIPCC) else "hipcc", "--offload-arch=gfx950", "-O3",
-                    "-std=c++17", "-I" + os.path.join(REPO, "native", "kernels"),
-                    "--cuda-device-only", "-S",
-                    os.path.join(REPO, "native", "kernels", "gemm_mxfp4.hip"), "-o", out],
-                   check=True, capture_output=True)
-    with open(out) as f:
-        asm = f.read()
+@pytest.mark.skipif(not mx.HIPCC, reason="no hipcc")
+def test_gemm_kernel_has_no_scratch_and_uses_the_scaled_mfma_on_e2m1():
+    asm, by = mx.kernel_listing(mx.MXFP4)
     mfma = re.findall(r"v_mfma_scale_f32_32x32x64_f8f6f4[^\n]*", asm)
     assert mfma and all("cbsz:4" in m and "blgp:4" in m for m in mfma), mfma[:3]
-    meta = re.findall(r"\.name:\s+(\S+)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)", asm)
-    by = {n: int(v) for n, v in meta}
     gemm = [n for n in by if "gemm" in n]
     assert len(gemm) == 1 and "mxk_gemm_mxfp4_tn_kernel" in gemm[0], by
-    quant = [n for n in by if "quantize_mxfp4_kernel" in n]
-    assert len(quant) == 2 and len(by) == 3, by
-    assert all(v == 0 for v in by.values()), by
-    for key in ("vgpr_spill_count", "sgpr_spill_count"):
-        spills = re.findall(r"\.%s:\s+(\d+)" % key, asm)
-        assert len(spills) == 3 and all(int(x) == 0 for x in spills), (key, spills)
+    rows = mx.check_quantiser_kernels(mx.MXFP4, by, "quantize_rows_kernel", 2)   # vector, element-wise
+    tr = mx.check_quantiser_kernels(mx.MXFP4, by, "quantize_tr_kernel", 4)
+    assert sorted(by) == sorted(gemm + rows + tr)            # 7 kernels and no other
+    assert all(v == 0 for m in by.values() for v in m.values()), by
 
 
 def test_host_sweep_of_the_format_header():

@@ -3,13 +3,11 @@ quantiser, the op's contract, validator and chart plumbing, build hygiene of
 ``native/kernels/gemm_mxfp8.hip``."""
 import json
 import os
-import re
-import shutil
-import subprocess
 
 import pytest
 import torch
 
+import mx_gemm_checks as mx
 import mxk8s.validate.__main__ as V
 from mx_gemm_checks import BF16_LINE, fake_bench, run_validator
 from mxk8s import config
@@ -19,7 +17,6 @@ from mxk8s.ops.mxfp8 import (dequantize_mxfp8, gemm_mxfp8_tn, is_fast_shape_mxfp
                              quantize_mxfp8_ref)
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
 def _wide(rows, K, seed, lo=-40, hi=40):
@@ -291,23 +288,12 @@ def test_chart_schema_rejects_unknown_dtype():
 
 
 # ---- build hygiene ----------------------------------------------------------------
-@pytest.mark.skipif(not os.path.exists(HIPCC) and not shutil.which("hipcc"), reason="no hipcc")
-def test_gemm_kernel_has_no_scratch_and_uses_the_scaled_mfma(tmp_path):
-    out = str(tmp_path / "m.s")
-    subprocess.run([HIPCC if os.path.exists(HIPCC) else "hipcc", "--offload-arch=gfx950", "-O3",
-                    "-std=c++17", "-I" + os.path.join(REPO, "native", "kernels"),
-                    "--cuda-device-only", "-S",
-                    os.path.join(REPO, "native", "kernels", "gemm_mxfp8.hip"), "-o", out],
-                   check=True, capture_output=True)
-    with open(out) as f:
-        asm = f.read()
+@pytest.mark.skipif(not mx.HIPCC, reason="no hipcc")
+def test_gemm_kernel_has_no_scratch_and_uses_the_scaled_mfma():
+    asm, by = mx.kernel_listing(mx.MXFP8)
     assert "v_mfma_scale_f32_32x32x64_f8f6f4" in asm
-    meta = re.findall(r"\.name:\s+(\S+)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)", asm)
-    by = {n: int(v) for n, v in meta}
     gemm = [n for n in by if "mxk_gemm_mxfp8_tn_kernel" in n]
     assert len(gemm) == 1, by
-    assert by[gemm[0]] == 0, by
-    quant = [n for n in by if "quantize_mxfp8_kernel" in n]
-    assert len(quant) == 2 and all(by[n] == 0 for n in quant), by
-    spills = re.findall(r"\.vgpr_spill_count:\s+(\d+)", asm)
-    assert spills and all(int(x) == 0 for x in spills), spills
+    assert by[gemm[0]]["private_segment_fixed_size"] == 0, by
+    mx.check_quantiser_kernels(mx.MXFP8, by, "quantize_rows_kernel", 2)   # vector, element-wise
+    assert all(v["vgpr_spill_count"] == 0 for v in by.values()), by
