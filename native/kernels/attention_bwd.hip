@@ -12,7 +12,7 @@
 //      S^T = K.Q^T and dP^T = V.dO^T with the query on the lane, P^T from the
 //      saved LSE (no max/sum), dS^T = P^T (dP^T - delta), dQ^T += K^T.dS^T
 //      (K^T by ds_read_b64_tr_b16 from the same swizzled image).
-//   3. dK/dV, key-parallel: one workgroup = 4 waves x 32 keys of one
+//   3. dK/dV, key-parallel: one workgroup = 8 waves x 16 keys of one
 //      (batch, q-head), sweeping 64-query slices: S = Q.K^T and dP = dO.V^T
 //      with the KEY on the lane, so P and dS are already the B operands of
 //      dV^T += dO^T.P and dK^T += Q^T.dS (dO^T, Q^T by transposed reads);
@@ -26,11 +26,6 @@
 // ===========================================================================
 namespace {
 constexpr int BQB = 64;   // queries per slice in the dK/dV kernel
-
-__device__ __forceinline__ void zero16(f32x16_t& x) {
-#pragma unroll
-  for (int r = 0; r < 16; ++r) x[r] = 0.f;
-}
 }  // namespace
 
 __global__ void __launch_bounds__(256)
@@ -203,7 +198,7 @@ mxk_attn_bwd_dq_kernel(const uint16_t* __restrict__ q, const uint16_t* __restric
     for (int s = 0; s < 8; ++s) asm volatile("" ::"v"(qf[s]), "v"(dof[s]));
     asm volatile("" ::"v"(lse2), "v"(dlt));
     if constexpr (DOC) asm volatile("" ::"v"(ds_row));
-    vm_wait0();
+    vm_wait<0>();
   } else {
     load_tile(0);
     store_tile(0);
@@ -218,290 +213,165 @@ mxk_attn_bwd_dq_kernel(const uint16_t* __restrict__ q, const uint16_t* __restric
   const int tr_ch = 2 * (G & 1) + ((i16 & 3) >> 1);
   const int tr_byte = 8 * (i16 & 1);
 
-  if constexpr (!UNROLL) {
-  for (int j = j_lo; j < nkv; ++j) {
-    const int buf = j & 1;
-    // DMA: buffer buf^1 was last read in iteration j-1 (barrier-certified)
-    if (j + 1 < nkv) {
-      if constexpr (DMA) issue(j + 1, buf ^ 1);
-      else load_tile(j + 1);
-    }
-    const int kv0 = j * BKV;
-    bool active = !CAUSAL || kv0 <= qw0 + 31;
-    if constexpr (DOC) active = active && attn_doc_tile_active(kv0, BKV, ds_w0);
-    if (active) {
-      const char* kt = smem[buf];
-      const char* vt = smem[buf] + TILE_BYTES;
-      const bool diag = CAUSAL && kv0 + BKV - 1 > qw0;
-      if constexpr (PIPE) {
-        // software-pipelined as the dK/dV kernel's PIPE body: S / dP operands
-        // read a half (4 k-steps) ahead, dS-side transposed reads issued
-        // under the exp, the next half's first operands under the dQ MFMAs
-        bf16x8_t ka[2][2], va[2][2];    // ring of two k-step pairs
-        auto read_p = [&](int kh, int pr, int slot) {
+  // One loop body for both walks.  UNROLL: two tiles per trip of the outer
+  // loop, so the buffer - and with it every LDS read address - is a
+  // compile-time constant (as in the forward's variant 4).  The do / while is
+  // no loop at all when UNROLL is false (the compiler's front end drops a
+  // constant-false back edge, and every such instance keeps the instruction
+  // stream of a plain `for (j)` around the body), and is unrolled in full
+  // when it is true.  Neither a `for (u < NU)` around the body nor the body as
+  // a lambda called from two loops does that: profiles/attention_dedup/.
+  constexpr int NU = UNROLL ? 2 : 1;
+  for (int j0 = j_lo; j0 < nkv; j0 += NU) {
+    int u = 0;
 #pragma unroll
-          for (int e = 0; e < 2; ++e) {
-            const int s = 2 * pr + e;
-            ka[slot][e] = lds_b128(kt + swz(32 * kh + r32, 2 * s + h));
-            va[slot][e] = lds_b128(vt + swz(32 * kh + r32, 2 * s + h));
-          }
-        };
-        auto read_t = [&](int kh, int db, int kk) {
-          const int key = 32 * kh + 16 * kk + tr_key;
-          const int ch = 4 * db + tr_ch;
-          return cat8(lds_tr_b64(kt + swz(key, ch) + tr_byte), lds_tr_b64(kt + swz(key + 8, ch) + tr_byte));
-        };
-        read_p(0, 0, 0);
+    do {
+      const int j = UNROLL ? j0 + u : j0;
+      const int buf = UNROLL ? u : j & 1;
+      if (!UNROLL || j < nkv) {
+        // DMA: buffer buf^1 was last read in iteration j-1 (barrier-certified)
+        if (j + 1 < nkv) {
+          if constexpr (DMA) issue(j + 1, buf ^ 1);
+          else load_tile(j + 1);
+        }
+        const int kv0 = j * BKV;
+        bool active = !CAUSAL || kv0 <= qw0 + 31;
+        if constexpr (DOC) active = active && attn_doc_tile_active(kv0, BKV, ds_w0);
+        if (active) {
+          const char* kt = smem[buf];
+          const char* vt = smem[buf] + TILE_BYTES;
+          const bool diag = CAUSAL && kv0 + BKV - 1 > qw0;
+          if constexpr (PIPE) {
+            // software-pipelined as the dK/dV kernel's PIPE body: S / dP operands
+            // read a half (4 k-steps) ahead, dS-side transposed reads issued
+            // under the exp, the next half's first operands under the dQ MFMAs
+            bf16x8_t ka[2][2], va[2][2];    // ring of two k-step pairs
+            auto read_p = [&](int kh, int pr, int slot) {
 #pragma unroll
-        for (int kh = 0; kh < 2; ++kh) {
-          __builtin_amdgcn_sched_barrier(0);
-          f32x16_t s0, p0;
-          zero16(s0);
-          zero16(p0);
-          bf16x8_t ta[8];
+              for (int e = 0; e < 2; ++e) {
+                const int s = 2 * pr + e;
+                ka[slot][e] = lds_b128(kt + swz(32 * kh + r32, 2 * s + h));
+                va[slot][e] = lds_b128(vt + swz(32 * kh + r32, 2 * s + h));
+              }
+            };
+            auto read_t = [&](int kh, int db, int kk) {
+              const int key = 32 * kh + 16 * kk + tr_key;
+              const int ch = 4 * db + tr_ch;
+              return cat8(lds_tr_b64(kt + swz(key, ch) + tr_byte),
+                          lds_tr_b64(kt + swz(key + 8, ch) + tr_byte));
+            };
+            read_p(0, 0, 0);
 #pragma unroll
-          for (int pr = 0; pr < 4; ++pr) {
-            if (pr < 3) {
-              read_p(kh, pr + 1, (pr + 1) & 1);
-            } else {
-#pragma unroll
-              for (int x = 0; x < 4; ++x) ta[x] = read_t(kh, x >> 1, x & 1);
-            }
-#pragma unroll
-            for (int e = 0; e < 2; ++e) {
-              s0 = mfma32(ka[pr & 1][e], qf[2 * pr + e], s0);
-              p0 = mfma32(va[pr & 1][e], dof[2 * pr + e], p0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-          }
-#pragma unroll
-          for (int x = 4; x < 8; ++x) ta[x] = read_t(kh, x >> 1, x & 1);
-          // packed fp32 (v_pk_fma / v_pk_add / v_pk_mul): half the VALU issues
-#pragma unroll
-          for (int r = 0; r < 16; r += 2) {
-            f32x2_t x = {s0[r], s0[r + 1]};
-            x = __builtin_elementwise_fma(x, f32x2_t{c, c}, f32x2_t{-lse2, -lse2});
-            s0[r] = fexp2(x[0]);   // P^T
-            s0[r + 1] = fexp2(x[1]);
-          }
-          if (diag) {   // wave-uniform: only diagonal tiles pay for the mask
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-              if (kv0 + 32 * kh + crow(r, h) > myq) s0[r] = 0.f;
-          }
-          if constexpr (DOC) {
-            if (attn_doc_tile_masked(kv0, ds_w1)) {   // wave-uniform
-#pragma unroll
-              for (int r = 0; r < 16; ++r)
-                if (kv0 + 32 * kh + crow(r, h) < ds_row) s0[r] = 0.f;
-            }
-          }
-#pragma unroll
-          for (int r = 0; r < 16; r += 2) {
-            const f32x2_t pp = f32x2_t{p0[r], p0[r + 1]} - f32x2_t{dlt, dlt};
-            const f32x2_t d = f32x2_t{s0[r], s0[r + 1]} * pp;   // dS^T
-            s0[r] = d[0];
-            s0[r + 1] = d[1];
-          }
-          bf16x8_t df[2];
-          df[0] = pack8(s0, 0);
-          df[1] = pack8(s0, 8);
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int x = 0; x < 8; ++x) {
-            acc[x >> 1] = mfma32(ta[x], df[x & 1], acc[x >> 1]);
-            if (kh == 0 && x == 5) {
-              read_p(1, 0, 0);
+            for (int kh = 0; kh < 2; ++kh) {
               __builtin_amdgcn_sched_barrier(0);
-            }
-          }
-        }
-      } else {
-      // one 32-key half at a time keeps S^T / dP^T to 32 registers
+              f32x16_t s0, p0;
+              zero16(s0);
+              zero16(p0);
+              bf16x8_t ta[8];
 #pragma unroll
-      for (int kh = 0; kh < 2; ++kh) {
-        f32x16_t s0, p0;
-        zero16(s0);
-        zero16(p0);
+              for (int pr = 0; pr < 4; ++pr) {
+                if (pr < 3) {
+                  read_p(kh, pr + 1, (pr + 1) & 1);
+                } else {
 #pragma unroll
-        for (int s = 0; s < 8; ++s) {
-          const bf16x8_t kf = lds_b128(kt + swz(32 * kh + r32, 2 * s + h));
-          const bf16x8_t vf = lds_b128(vt + swz(32 * kh + r32, 2 * s + h));
-          s0 = mfma32(kf, qf[s], s0);
-          p0 = mfma32(vf, dof[s], p0);
-        }
+                  for (int x = 0; x < 4; ++x) ta[x] = read_t(kh, x >> 1, x & 1);
+                }
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          float e0 = fexp2(fmaf(s0[r], c, -lse2));
-          if (diag && kv0 + 32 * kh + crow(r, h) > myq) e0 = 0.f;
-          s0[r] = e0 * (p0[r] - dlt);   // dS^T
-        }
-        bf16x8_t df[2];
-        df[0] = pack8(s0, 0);
-        df[1] = pack8(s0, 8);
-        // dQ^T += K^T . dS^T  (K^T by transposed reads of the K image)
+                for (int e = 0; e < 2; ++e) {
+                  s0 = mfma32(ka[pr & 1][e], qf[2 * pr + e], s0);
+                  p0 = mfma32(va[pr & 1][e], dof[2 * pr + e], p0);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+              }
 #pragma unroll
-        for (int db = 0; db < 4; ++db) {
+              for (int x = 4; x < 8; ++x) ta[x] = read_t(kh, x >> 1, x & 1);
+              // packed fp32 (v_pk_fma / v_pk_add / v_pk_mul): half the VALU issues
 #pragma unroll
-          for (int kk = 0; kk < 2; ++kk) {
-            const int key = 32 * kh + 16 * kk + tr_key;
-            const int ch = 4 * db + tr_ch;
-            const bf16x4_t lo = lds_tr_b64(kt + swz(key, ch) + tr_byte);
-            const bf16x4_t hi = lds_tr_b64(kt + swz(key + 8, ch) + tr_byte);
-            const bf16x8_t a = cat8(lo, hi);
-            acc[db] = mfma32(a, df[kk], acc[db]);
-          }
-        }
-      }
-      }
-    }
-    if constexpr (DMA) {
-      vm_wait0();   // own pieces of tile j+1
-    } else {
-      if (j + 1 < nkv) store_tile(buf ^ 1);
-    }
-    __syncthreads();
-  }
-  } else {
-  // UNROLL: the loop body as a lambda called with a compile-time buffer, so
-  // the LDS read addresses are loop invariants (as in the forward's variant 4)
-  auto step = [&](int j, int buf) {
-    // DMA: buffer buf^1 was last read in iteration j-1 (barrier-certified)
-    if (j + 1 < nkv) {
-      if constexpr (DMA) issue(j + 1, buf ^ 1);
-      else load_tile(j + 1);
-    }
-    const int kv0 = j * BKV;
-    if (!CAUSAL || kv0 <= qw0 + 31) {
-      const char* kt = smem[buf];
-      const char* vt = smem[buf] + TILE_BYTES;
-      const bool diag = CAUSAL && kv0 + BKV - 1 > qw0;
-      if constexpr (PIPE) {
-        // software-pipelined as the dK/dV kernel's PIPE body: S / dP operands
-        // read a half (4 k-steps) ahead, dS-side transposed reads issued
-        // under the exp, the next half's first operands under the dQ MFMAs
-        bf16x8_t ka[2][2], va[2][2];    // ring of two k-step pairs
-        auto read_p = [&](int kh, int pr, int slot) {
+              for (int r = 0; r < 16; r += 2) {
+                f32x2_t x = {s0[r], s0[r + 1]};
+                x = __builtin_elementwise_fma(x, f32x2_t{c, c}, f32x2_t{-lse2, -lse2});
+                s0[r] = fexp2(x[0]);   // P^T
+                s0[r + 1] = fexp2(x[1]);
+              }
+              if (diag) {   // wave-uniform: only diagonal tiles pay for the mask
 #pragma unroll
-          for (int e = 0; e < 2; ++e) {
-            const int s = 2 * pr + e;
-            ka[slot][e] = lds_b128(kt + swz(32 * kh + r32, 2 * s + h));
-            va[slot][e] = lds_b128(vt + swz(32 * kh + r32, 2 * s + h));
-          }
-        };
-        auto read_t = [&](int kh, int db, int kk) {
-          const int key = 32 * kh + 16 * kk + tr_key;
-          const int ch = 4 * db + tr_ch;
-          return cat8(lds_tr_b64(kt + swz(key, ch) + tr_byte), lds_tr_b64(kt + swz(key + 8, ch) + tr_byte));
-        };
-        read_p(0, 0, 0);
+                for (int r = 0; r < 16; ++r)
+                  if (kv0 + 32 * kh + crow(r, h) > myq) s0[r] = 0.f;
+              }
+              if constexpr (DOC) {
+                if (attn_doc_tile_masked(kv0, ds_w1)) {   // wave-uniform
 #pragma unroll
-        for (int kh = 0; kh < 2; ++kh) {
-          __builtin_amdgcn_sched_barrier(0);
-          f32x16_t s0, p0;
-          zero16(s0);
-          zero16(p0);
-          bf16x8_t ta[8];
+                  for (int r = 0; r < 16; ++r)
+                    if (kv0 + 32 * kh + crow(r, h) < ds_row) s0[r] = 0.f;
+                }
+              }
 #pragma unroll
-          for (int pr = 0; pr < 4; ++pr) {
-            if (pr < 3) {
-              read_p(kh, pr + 1, (pr + 1) & 1);
-            } else {
-#pragma unroll
-              for (int x = 0; x < 4; ++x) ta[x] = read_t(kh, x >> 1, x & 1);
-            }
-#pragma unroll
-            for (int e = 0; e < 2; ++e) {
-              s0 = mfma32(ka[pr & 1][e], qf[2 * pr + e], s0);
-              p0 = mfma32(va[pr & 1][e], dof[2 * pr + e], p0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-          }
-#pragma unroll
-          for (int x = 4; x < 8; ++x) ta[x] = read_t(kh, x >> 1, x & 1);
-          // packed fp32 (v_pk_fma / v_pk_add / v_pk_mul): half the VALU issues
-#pragma unroll
-          for (int r = 0; r < 16; r += 2) {
-            f32x2_t x = {s0[r], s0[r + 1]};
-            x = __builtin_elementwise_fma(x, f32x2_t{c, c}, f32x2_t{-lse2, -lse2});
-            s0[r] = fexp2(x[0]);   // P^T
-            s0[r + 1] = fexp2(x[1]);
-          }
-          if (diag) {   // wave-uniform: only diagonal tiles pay for the mask
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-              if (kv0 + 32 * kh + crow(r, h) > myq) s0[r] = 0.f;
-          }
-#pragma unroll
-          for (int r = 0; r < 16; r += 2) {
-            const f32x2_t pp = f32x2_t{p0[r], p0[r + 1]} - f32x2_t{dlt, dlt};
-            const f32x2_t d = f32x2_t{s0[r], s0[r + 1]} * pp;   // dS^T
-            s0[r] = d[0];
-            s0[r + 1] = d[1];
-          }
-          bf16x8_t df[2];
-          df[0] = pack8(s0, 0);
-          df[1] = pack8(s0, 8);
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int x = 0; x < 8; ++x) {
-            acc[x >> 1] = mfma32(ta[x], df[x & 1], acc[x >> 1]);
-            if (kh == 0 && x == 5) {
-              read_p(1, 0, 0);
+              for (int r = 0; r < 16; r += 2) {
+                const f32x2_t pp = f32x2_t{p0[r], p0[r + 1]} - f32x2_t{dlt, dlt};
+                const f32x2_t d = f32x2_t{s0[r], s0[r + 1]} * pp;   // dS^T
+                s0[r] = d[0];
+                s0[r + 1] = d[1];
+              }
+              bf16x8_t df[2];
+              df[0] = pack8(s0, 0);
+              df[1] = pack8(s0, 8);
               __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+              for (int x = 0; x < 8; ++x) {
+                acc[x >> 1] = mfma32(ta[x], df[x & 1], acc[x >> 1]);
+                if (kh == 0 && x == 5) {
+                  read_p(1, 0, 0);
+                  __builtin_amdgcn_sched_barrier(0);
+                }
+              }
+            }
+          } else {
+          // one 32-key half at a time keeps S^T / dP^T to 32 registers
+#pragma unroll
+          for (int kh = 0; kh < 2; ++kh) {
+            f32x16_t s0, p0;
+            zero16(s0);
+            zero16(p0);
+#pragma unroll
+            for (int s = 0; s < 8; ++s) {
+              const bf16x8_t kf = lds_b128(kt + swz(32 * kh + r32, 2 * s + h));
+              const bf16x8_t vf = lds_b128(vt + swz(32 * kh + r32, 2 * s + h));
+              s0 = mfma32(kf, qf[s], s0);
+              p0 = mfma32(vf, dof[s], p0);
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+              float e0 = fexp2(fmaf(s0[r], c, -lse2));
+              if (diag && kv0 + 32 * kh + crow(r, h) > myq) e0 = 0.f;
+              s0[r] = e0 * (p0[r] - dlt);   // dS^T
+            }
+            bf16x8_t df[2];
+            df[0] = pack8(s0, 0);
+            df[1] = pack8(s0, 8);
+            // dQ^T += K^T . dS^T  (K^T by transposed reads of the K image)
+#pragma unroll
+            for (int db = 0; db < 4; ++db) {
+#pragma unroll
+              for (int kk = 0; kk < 2; ++kk) {
+                const int key = 32 * kh + 16 * kk + tr_key;
+                const int ch = 4 * db + tr_ch;
+                const bf16x4_t lo = lds_tr_b64(kt + swz(key, ch) + tr_byte);
+                const bf16x4_t hi = lds_tr_b64(kt + swz(key + 8, ch) + tr_byte);
+                const bf16x8_t a = cat8(lo, hi);
+                acc[db] = mfma32(a, df[kk], acc[db]);
+              }
             }
           }
-        }
-      } else {
-      // one 32-key half at a time keeps S^T / dP^T to 32 registers
-#pragma unroll
-      for (int kh = 0; kh < 2; ++kh) {
-        f32x16_t s0, p0;
-        zero16(s0);
-        zero16(p0);
-#pragma unroll
-        for (int s = 0; s < 8; ++s) {
-          const bf16x8_t kf = lds_b128(kt + swz(32 * kh + r32, 2 * s + h));
-          const bf16x8_t vf = lds_b128(vt + swz(32 * kh + r32, 2 * s + h));
-          s0 = mfma32(kf, qf[s], s0);
-          p0 = mfma32(vf, dof[s], p0);
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          float e0 = fexp2(fmaf(s0[r], c, -lse2));
-          if (diag && kv0 + 32 * kh + crow(r, h) > myq) e0 = 0.f;
-          s0[r] = e0 * (p0[r] - dlt);   // dS^T
-        }
-        bf16x8_t df[2];
-        df[0] = pack8(s0, 0);
-        df[1] = pack8(s0, 8);
-        // dQ^T += K^T . dS^T  (K^T by transposed reads of the K image)
-#pragma unroll
-        for (int db = 0; db < 4; ++db) {
-#pragma unroll
-          for (int kk = 0; kk < 2; ++kk) {
-            const int key = 32 * kh + 16 * kk + tr_key;
-            const int ch = 4 * db + tr_ch;
-            const bf16x4_t lo = lds_tr_b64(kt + swz(key, ch) + tr_byte);
-            const bf16x4_t hi = lds_tr_b64(kt + swz(key + 8, ch) + tr_byte);
-            const bf16x8_t a = cat8(lo, hi);
-            acc[db] = mfma32(a, df[kk], acc[db]);
           }
         }
+        if constexpr (DMA) {
+          vm_wait<0>();   // own pieces of tile j+1
+        } else {
+          if (j + 1 < nkv) store_tile(buf ^ 1);
+        }
+        __syncthreads();
       }
-      }
-    }
-    if constexpr (DMA) {
-      vm_wait0();   // own pieces of tile j+1
-    } else {
-      if (j + 1 < nkv) store_tile(buf ^ 1);
-    }
-    __syncthreads();
-  };
-  for (int j = 0; j < nkv; j += 2) {
-    step(j, 0);
-    if (j + 1 < nkv) step(j + 1, 1);
-  }
+    } while (UNROLL && ++u < NU);
   }
   uint16_t* row = dq + (static_cast<long>(b) * S + myq) * Hq * D + static_cast<long>(hq) * D;
   // 16-B stores, lane halves paired by v_permlane32_swap (as the forward's O)
@@ -526,200 +396,30 @@ mxk_attn_bwd_dq_kernel(const uint16_t* __restrict__ q, const uint16_t* __restric
   }
 }
 
-// dK/dV for 128 keys of one (batch, q-head); partials dk_p/dv_p are fp32
-// [B, S, Hq, 128] (summed over the GQA group afterwards).
-template <bool CAUSAL>
-__global__ void __launch_bounds__(NT, 1)
-mxk_attn_bwd_dkdv_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
-                         const uint16_t* __restrict__ v, const uint16_t* __restrict__ dout,
-                         const float* __restrict__ lse, const float* __restrict__ delta,
-                         float* __restrict__ dk_p, float* __restrict__ dv_p, int S, int Hq,
-                         int Hkv, long q_tok, long k_tok, long v_tok, float scale) {
-  // [buf][Q tile 64x128 | dO tile 64x128] + lse/delta slices
-  __shared__ __attribute__((aligned(16))) char smem[2][2 * BQB * 256];
-  __shared__ __attribute__((aligned(16))) float srow[2][2][BQB];   // [buf][lse*log2e/c | delta]
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int r32 = lane & 31;
-  const int h = lane >> 5;
-
-  const int nkb = S / BQ;   // 128-key blocks
-  int bh, kb;
-  {
-    // key block kb has (nkb - kb) query blocks of work: heaviest = kb 0
-    int qbi;
-    map_block(blockIdx.x, gridDim.x / nkb, nkb, CAUSAL, &bh, &qbi);
-    kb = CAUSAL ? nkb - 1 - qbi : qbi;
-  }
-  const int b = bh / Hq, hq = bh % Hq;
-  const int hkv = hq / (Hq / Hkv);
-  const int k0 = kb * BQ;
-  const int kw0 = k0 + wave * 32;
-  const int mykey = kw0 + r32;
-
-  const uint16_t* qb_ptr = q + static_cast<long>(b) * S * q_tok + static_cast<long>(hq) * D;
-  const uint16_t* dob_ptr = dout + static_cast<long>(b) * S * Hq * D + static_cast<long>(hq) * D;
-  const uint16_t* kb_ptr = k + static_cast<long>(b) * S * k_tok + static_cast<long>(hkv) * D;
-  const uint16_t* vb_ptr = v + static_cast<long>(b) * S * v_tok + static_cast<long>(hkv) * D;
-  const float* lse_b = lse + (static_cast<long>(b) * Hq + hq) * S;
-  const float* dl_b = delta + (static_cast<long>(b) * Hq + hq) * S;
-
-  // K^T / V^T fragments (B operands of S = Q.K^T and dP = dO.V^T)
-  bf16x8_t kf[8], vf[8];
-#pragma unroll
-  for (int s = 0; s < 8; ++s) {
-    kf[s] = *reinterpret_cast<const bf16x8_t*>(kb_ptr + static_cast<long>(mykey) * k_tok + 16 * s + 8 * h);
-    vf[s] = *reinterpret_cast<const bf16x8_t*>(vb_ptr + static_cast<long>(mykey) * v_tok + 16 * s + 8 * h);
-  }
-  const float c = scale * 1.4426950408889634f;
-  const float inv_c = 1.f / c;
-
-  const int q_begin = CAUSAL ? k0 : 0;
-  const int nsl = (S - q_begin) / BQB;
-  const int ld_row = tid >> 4, ld_ch = tid & 15;
-  bf16x8_t qst[4], dst[4];
-  float rst = 0.f;
-  auto load_slice = [&](int t) {
-    const long r0 = q_begin + static_cast<long>(t) * BQB + ld_row;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      qst[i] = *reinterpret_cast<const bf16x8_t*>(qb_ptr + (r0 + 16 * i) * q_tok + ld_ch * 8);
-      dst[i] = *reinterpret_cast<const bf16x8_t*>(dob_ptr + (r0 + 16 * i) * Hq * D + ld_ch * 8);
-    }
-    if (tid < 2 * BQB) {
-      const long qi = q_begin + static_cast<long>(t) * BQB + (tid & (BQB - 1));
-      rst = tid < BQB ? -lse_b[qi] * 1.4426950408889634f * inv_c : -dl_b[qi];
-    }
-  };
-  auto store_slice = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int off = swz(ld_row + 16 * i, ld_ch);
-      *reinterpret_cast<bf16x8_t*>(smem[buf] + off) = qst[i];
-      *reinterpret_cast<bf16x8_t*>(smem[buf] + BQB * 256 + off) = dst[i];
-    }
-    if (tid < 2 * BQB) srow[buf][tid / BQB][tid & (BQB - 1)] = rst;
-  };
-  load_slice(0);
-  store_slice(0);
-  __syncthreads();
-
-  f32x16_t dka[4], dva[4];
-#pragma unroll
-  for (int db = 0; db < 4; ++db) { zero16(dka[db]); zero16(dva[db]); }
-  const int G = lane >> 4, i16 = lane & 15;
-  const int tr_row = 4 * h + (i16 >> 2);
-  const int tr_ch = 2 * (G & 1) + ((i16 & 3) >> 1);
-  const int tr_byte = 8 * (i16 & 1);
-
-  for (int t = 0; t < nsl; ++t) {
-    const int buf = t & 1;
-    if (t + 1 < nsl) load_slice(t + 1);
-    const int qs0 = q_begin + t * BQB;
-    if (!CAUSAL || qs0 + BQB - 1 >= kw0) {
-      const char* qt = smem[buf];
-      const char* dt = smem[buf] + BQB * 256;
-      // accumulator init: -LSE/scale (S) and -delta (dP) per query row
-      f32x16_t s0, s1, p0, p1;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int qr = 8 * g + 4 * h;
-        const float4 l0 = *reinterpret_cast<const float4*>(&srow[buf][0][qr]);
-        const float4 l1 = *reinterpret_cast<const float4*>(&srow[buf][0][32 + qr]);
-        const float4 d0 = *reinterpret_cast<const float4*>(&srow[buf][1][qr]);
-        const float4 d1 = *reinterpret_cast<const float4*>(&srow[buf][1][32 + qr]);
-        s0[4 * g] = l0.x; s0[4 * g + 1] = l0.y; s0[4 * g + 2] = l0.z; s0[4 * g + 3] = l0.w;
-        s1[4 * g] = l1.x; s1[4 * g + 1] = l1.y; s1[4 * g + 2] = l1.z; s1[4 * g + 3] = l1.w;
-        p0[4 * g] = d0.x; p0[4 * g + 1] = d0.y; p0[4 * g + 2] = d0.z; p0[4 * g + 3] = d0.w;
-        p1[4 * g] = d1.x; p1[4 * g + 1] = d1.y; p1[4 * g + 2] = d1.z; p1[4 * g + 3] = d1.w;
-      }
-#pragma unroll
-      for (int s = 0; s < 8; ++s) {
-        const bf16x8_t q0f = lds_b128(qt + swz(r32, 2 * s + h));
-        const bf16x8_t q1f = lds_b128(qt + swz(32 + r32, 2 * s + h));
-        const bf16x8_t o0f = lds_b128(dt + swz(r32, 2 * s + h));
-        const bf16x8_t o1f = lds_b128(dt + swz(32 + r32, 2 * s + h));
-        s0 = mfma32(q0f, kf[s], s0);
-        s1 = mfma32(q1f, kf[s], s1);
-        p0 = mfma32(o0f, vf[s], p0);
-        p1 = mfma32(o1f, vf[s], p1);
-      }
-      const bool diag = CAUSAL && qs0 < kw0 + 31;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int qi = qs0 + crow(r, h);
-        float e0 = fexp2(s0[r] * c);
-        float e1 = fexp2(s1[r] * c);
-        if (diag && mykey > qi) e0 = 0.f;
-        if (diag && mykey > qi + 32) e1 = 0.f;
-        s0[r] = e0;                 // P
-        s1[r] = e1;
-        p0[r] = e0 * p0[r];         // dS = P (dP - delta)
-        p1[r] = e1 * p1[r];
-      }
-      bf16x8_t pf[4], sf[4];
-      pf[0] = pack8(s0, 0); pf[1] = pack8(s0, 8); pf[2] = pack8(s1, 0); pf[3] = pack8(s1, 8);
-      sf[0] = pack8(p0, 0); sf[1] = pack8(p0, 8); sf[2] = pack8(p1, 0); sf[3] = pack8(p1, 8);
-      // dV^T += dO^T . P ; dK^T += Q^T . dS   (transposed reads of dO / Q)
-#pragma unroll
-      for (int db = 0; db < 4; ++db) {
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-          const int row = 16 * ks + tr_row;
-          const int ch = 4 * db + tr_ch;
-          const bf16x4_t olo = lds_tr_b64(dt + swz(row, ch) + tr_byte);
-          const bf16x4_t ohi = lds_tr_b64(dt + swz(row + 8, ch) + tr_byte);
-          const bf16x4_t qlo = lds_tr_b64(qt + swz(row, ch) + tr_byte);
-          const bf16x4_t qhi = lds_tr_b64(qt + swz(row + 8, ch) + tr_byte);
-          const bf16x8_t ao = cat8(olo, ohi);
-          const bf16x8_t aq = cat8(qlo, qhi);
-          dva[db] = mfma32(ao, pf[ks], dva[db]);
-          dka[db] = mfma32(aq, sf[ks], dka[db]);
-        }
-      }
-    }
-    if (t + 1 < nsl) store_slice(buf ^ 1);
-    __syncthreads();
-  }
-  // partials: lane = key, registers = dims
-  const long prow = ((static_cast<long>(b) * S + mykey) * Hq + hq) * D;
-#pragma unroll
-  for (int db = 0; db < 4; ++db) {
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int d = 32 * db + 8 * g + 4 * h;
-      *reinterpret_cast<float4*>(dk_p + prow + d) =
-          make_float4(dka[db][4 * g] * scale, dka[db][4 * g + 1] * scale,
-                      dka[db][4 * g + 2] * scale, dka[db][4 * g + 3] * scale);
-      *reinterpret_cast<float4*>(dv_p + prow + d) =
-          make_float4(dva[db][4 * g], dva[db][4 * g + 1], dva[db][4 * g + 2], dva[db][4 * g + 3]);
-    }
-  }
-}
-
-// Round-2 alternatives measured against the PIPE body of this kernel
-// (profiles/r2_attention/): a four-buffer LDS ring with every load three
-// items ahead (lse / delta rows by DMA too) 1.129 vs 1.099 ms per layer, and
-// a pipelined 32-key-per-wave kernel (4 waves, one per SIMD, half the LDS
-// operand traffic, dK / dV pinned to AGPRs, softmax overlapped in-wave)
-// 1.182 vs 1.107 ms - two waves per SIMD hide more than the halved LDS
-// traffic saves.  Also neutral: 128-query slices (half the barriers and
-// pipeline drains; 1.1249 vs 1.1215 ms, bit-identical).  A staggered order
-// for waves 4-7 (both S / dP groups first, so the SIMD partners' exp phases
-// do not coincide) needs ~16 more VGPRs than the 223 of this body and
-// spilled (119 VGPRs, 4.17 ms).
 // dK/dV with 16x16x32 MFMAs: one workgroup = 8 waves x 16 keys (128 keys of
 // one (batch, q-head)), so a wave holds dK^T / dV^T of its keys in 64
-// registers (32x32 tiles need 128) and two waves share each SIMD - the
-// 32-key kernel above runs one wave per SIMD and leaves the matrix core idle
-// through its exp / pack / LDS phases.  Per 32-query k-step:
+// registers (32x32 tiles need 128) and two waves share each SIMD - a
+// 32-key-per-wave kernel on 32x32x16 MFMAs (4 waves, one per SIMD; removed)
+// left the matrix core idle through its exp / pack / LDS phases.  Per
+// 32-query k-step:
 //   S  = Q.K^T, dP = dO.V^T    (A: Q / dO rows, ds_read_b128; B: K / V in registers)
 //   P  = exp2(c S'), dS = P dP' (accumulators pre-loaded with -LSE/scale, -delta)
 //   dV^T += dO^T.P, dK^T += Q^T.dS  (A: transposed reads of the same images;
 //   B: two 16x16 accumulator tiles = 8 consecutive-by-4 queries per lane)
 // Q / dO image: 256-B rows, chunk c of row r at c ^ 2(r & 7) - conflict-free
 // for the 16x16x32 row reads and the transposed reads (tests/test_attention_layout.py).
+// Partials dk_p / dv_p (without GQA) are fp32 [B, S, Hq, 128], summed over the
+// GQA group afterwards.
+// Round-2 alternatives measured against the PIPE body of this kernel
+// (profiles/r2_attention/): a four-buffer LDS ring with every load three
+// items ahead (lse / delta rows by DMA too) 1.129 vs 1.099 ms per layer, and
+// the 32-key-per-wave kernel pipelined (half the LDS operand traffic, dK / dV
+// pinned to AGPRs, softmax overlapped in-wave) 1.182 vs 1.107 ms - two waves
+// per SIMD hide more than the halved LDS traffic saves.  Also neutral:
+// 128-query slices (half the barriers and pipeline drains; 1.1249 vs
+// 1.1215 ms, bit-identical).  A staggered order for waves 4-7 (both S / dP
+// groups first, so the SIMD partners' exp phases do not coincide) needs ~16
+// more VGPRs than the 223 of this body and spilled (119 VGPRs, 4.17 ms).
 namespace {
 __device__ __forceinline__ int swz16(int row, int ch) {
   return row * 256 + ((ch ^ (2 * (row & 7))) << 4);
@@ -916,7 +616,7 @@ mxk_attn_bwd_dkdv16_kernel(const uint16_t* __restrict__ q, const uint16_t* __res
   if constexpr (DMA) {
     issue(0, 0);
     load_row(0);
-    vm_wait0();
+    vm_wait<0>();
     store_row(0);
   } else {
     load_slice(0);
@@ -1097,7 +797,7 @@ mxk_attn_bwd_dkdv16_kernel(const uint16_t* __restrict__ q, const uint16_t* __res
       }
     }
     if constexpr (DMA) {
-      vm_wait0();   // own pieces of item i+1
+      vm_wait<0>();   // own pieces of item i+1
       if (i + 1 < niter) store_row(buf ^ 1);
     } else {
       if (i + 1 < niter) store_slice(buf ^ 1);

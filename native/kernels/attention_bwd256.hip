@@ -77,39 +77,9 @@ __device__ __forceinline__ void dma4m(const mxk::u32x4& rsrc, uint32_t lds_addr,
                : "memory");
 }
 
-// s_waitcnt vmcnt(N) (expcnt / lgkmcnt untouched)
-template <int N>
-__device__ __forceinline__ void vm_wait() {
-  static_assert(N >= 0 && N < 64, "vmcnt range");
-  __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (15 << 8) | ((N >> 4) << 14));
-}
-
-// dK^T / dV^T accumulation with the accumulators pinned to AGPRs (inline
-// asm, "+a"): all 256 accumulator registers hold dK^T / dV^T for the whole
-// kernel, so S / dP - which the VALU reads - stay in VGPRs.  The asm is
-// opaque to hipcc's hazard recognizer; its operands are either LDS-read
-// results (no VALU hazard) or the bf16 P / dS operands, which
-// mfma_operands_ready() fences with the VALU-write -> MFMA-read wait states.
-__device__ __forceinline__ void mfma_acc(f32x16_t& acc, const bf16x8_t& a, const bf16x8_t& b) {
-  asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
-}
-// S / dP chains, accumulators pinned to VGPRs ("+v"): the VALU reads them,
-// so they must not be allocated in (or shuffled through) the accumulator
-// file.  FENCE: the first MFMA of a chain whose C or operands a VALU
-// instruction may just have written.
-template <bool FENCE = false>
-__device__ __forceinline__ void mfma_v(f32x16_t& acc, const bf16x8_t& a, const bf16x8_t& b) {
-  if constexpr (FENCE)
-    asm volatile("s_nop 2\n\tv_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
-  else
-    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
-}
-// after the last MFMA of an S / dP chain: the XDL-write -> VALU-read wait
-// states (8-pass 32x32x16: 12) before anything reads the results, and the
-// results redefined behind the nops so no reader is scheduled above them
-__device__ __forceinline__ void mfma_result_fence(f32x16_t& x, f32x16_t& y) {
-  asm volatile("s_nop 7\n\ts_nop 4" : "+v"(x), "+v"(y));
-}
+// The MFMA wrappers (dK^T / dV^T: mfma_a, all 256 accumulator registers for
+// the whole kernel; S / dP: mfma_v, their bf16 P / dS operands fenced by
+// mfma_operands_ready()), mfma_result_fence and vm_wait<N>: attention_common.h.
 // S' / dP' of both key tiles for one k-step, then 12 wait states, in one
 // statement
 __device__ __forceinline__ void mfma4_fenced(f32x16_t& s0, f32x16_t& p0, f32x16_t& s1,
@@ -125,9 +95,6 @@ __device__ __forceinline__ void mfma4_fenced(f32x16_t& s0, f32x16_t& p0, f32x16_
       "s_nop 7\n\ts_nop 4"
       : "+v"(s0), "+v"(p0), "+v"(s1), "+v"(p1)
       : "v"(qa), "v"(da), "v"(k0), "v"(k1), "v"(v0), "v"(v1));
-}
-__device__ __forceinline__ void mfma_result_fence1(f32x16_t& x) {
-  asm volatile("s_nop 7\n\ts_nop 4" : "+v"(x));
 }
 __device__ __forceinline__ void mfma_operands_ready(const bf16x8_t (&pf)[2], const bf16x8_t (&sf)[2]) {
   asm volatile("s_nop 2" ::"v"(pf[0]), "v"(pf[1]), "v"(sf[0]), "v"(sf[1]));
@@ -174,11 +141,6 @@ __device__ __forceinline__ void lds_barrier() {
 // transposed K reads (the V^T pattern of the forward) deliver them
 __device__ __forceinline__ int dspos(int key) {
   return (key & ~12) | ((key & 4) << 1) | ((key & 8) >> 1);
-}
-
-__device__ __forceinline__ void zero16(f32x16_t& x) {
-#pragma unroll
-  for (int r = 0; r < 16; ++r) x[r] = 0.f;
 }
 }  // namespace
 
@@ -401,7 +363,7 @@ mxk_attn_bwd_dkdv256_kernel(const uint16_t* __restrict__ q, const uint16_t* __re
       }
       if ((t & 3) == 3) __builtin_amdgcn_sched_barrier(0);   // bound the operand look-ahead
     }
-    mfma_result_fence1(acc);
+    mfma_result_fence(acc);
     // wave-uniform row base + one lane offset, so the atomics take the
     // SGPR-base + VGPR-offset form (no 64-bit address per register)
     const long row0 = (static_cast<long>(b) * S + qs0) * Hq + hq0 + gq;   // (b, qs0, head)
@@ -488,8 +450,8 @@ mxk_attn_bwd_dkdv256_kernel(const uint16_t* __restrict__ q, const uint16_t* __re
           no = tread(dt, i + 1);
           nq = tread(qt, i + 1);
         }
-        mfma_acc(dva[db][kt], ao, pf[s2]);
-        mfma_acc(dka[db][kt], aq, sf[s2]);
+        mfma_a(dva[db][kt], ao, pf[s2]);
+        mfma_a(dka[db][kt], aq, sf[s2]);
         beside(2 * db + s2);
         __builtin_amdgcn_sched_barrier(0);
         ao = no;

@@ -26,12 +26,17 @@ __device__ __forceinline__ bf16x8_t lds_b128(const char* p) {
   return *reinterpret_cast<const bf16x8_t*>(p);
 }
 
-// s_waitcnt vmcnt(0) through the builtin rather than inline asm: the
-// compiler's wait-insertion pass then knows every earlier load has landed and
-// adds no waits of its own further on (with inline asm it re-waits, e.g. on a
-// register a finished load wrote - and such a wait also waits for the DMA of
-// the next tile, which the compiler cannot see).
-__device__ __forceinline__ void vm_wait0() { __builtin_amdgcn_s_waitcnt(0x0F70); }
+// s_waitcnt vmcnt(N) (expcnt / lgkmcnt untouched) through the builtin rather
+// than inline asm (mxk::vm_wait_n): the compiler's wait-insertion pass then
+// knows every load but the N youngest has landed and adds no waits of its own
+// further on (with inline asm it re-waits, e.g. on a register a finished load
+// wrote - and such a wait also waits for the DMA of the next tile, which the
+// compiler cannot see).
+template <int N>
+__device__ __forceinline__ void vm_wait() {
+  static_assert(N >= 0 && N < 64, "vmcnt range");
+  __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (15 << 8) | ((N >> 4) << 14));
+}
 
 __device__ __forceinline__ bf16x4_t lds_tr_b64(const char* p) {
   typedef short s4 __attribute__((ext_vector_type(4)));
@@ -118,6 +123,71 @@ __device__ __forceinline__ void map_block_xcd(int w, int nwg, int nqb, int grp, 
   const int j = r / grp;
   *bh = g * grp + (r - j * grp);
   *qb = causal ? nqb - 1 - j : j;
+}
+
+__device__ __forceinline__ void zero16(f32x16_t& x) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) x[r] = 0.f;
+}
+
+// ---- the one-wave-per-SIMD kernels (attention_fwd256 / _dq256 / _bwd256.hip)
+// K / V tiles of the forward and the dQ kernel: a 4-slot LDS ring, two tiles
+// of DMA lead, one barrier per tile
+constexpr int KT = 64;                     // keys per DMA tile
+constexpr int KV_SLOT = 2 * TILE_BYTES;    // K | V image of one tile (32 KiB)
+constexpr int KV_NSLOT = 4;
+constexpr int KV_RING = KV_NSLOT * KV_SLOT;   // 128 KiB
+
+// Their MFMAs are inline asm, so that the constraint pins the accumulator's
+// register file (the builtin's allocation shuffles accumulators between the
+// files).  The asm is opaque to hipcc's hazard recognizer: what an MFMA reads
+// is either an LDS-read result (no VALU hazard) or fenced by its kernel with
+// the VALU-write -> MFMA-read wait states (fops_ready, ds_ready,
+// mfma_operands_ready, or FENCE below); what the VALU reads of an MFMA's
+// result goes through mfma_result_fence first.
+//
+// Accumulator pinned to AGPRs ("+a"; O^T, dQ^T, dK^T / dV^T): the accumulator
+// file holds it for the whole kernel and the arch VGPRs stay free for the
+// tiles the VALU reads.
+__device__ __forceinline__ void mfma_a(f32x16_t& acc, const bf16x8_t& a, const bf16x8_t& b) {
+  asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
+}
+// Accumulator pinned to VGPRs ("+v"; S / dP chains): the VALU reads it, so it
+// must not be allocated in (or shuffled through) the accumulator file.
+// FENCE: the first MFMA of a chain whose C or operands a VALU instruction may
+// just have written.
+template <bool FENCE = false>
+__device__ __forceinline__ void mfma_v(f32x16_t& acc, const bf16x8_t& a, const bf16x8_t& b) {
+  if constexpr (FENCE)
+    asm volatile("s_nop 2\n\tv_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
+  else
+    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
+}
+// The same chain with the B operand (a Q / dO fragment) held in AGPRs, where
+// the fragments live for the whole kernel beside the pinned accumulators.
+// "+a" on the fragment: the AGPR copy is the live value (an "a" input alone
+// lets the allocator keep it in VGPRs and copy it in per MFMA).
+template <bool FENCE = false>
+__device__ __forceinline__ void mfma_vq(f32x16_t& acc, const bf16x8_t& a, bf16x8_t& bq) {
+  if constexpr (FENCE)
+    asm volatile("s_nop 2\n\tv_mfma_f32_32x32x16_bf16 %0, %2, %1, %0" : "+v"(acc), "+a"(bq) : "v"(a));
+  else
+    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %2, %1, %0" : "+v"(acc), "+a"(bq) : "v"(a));
+}
+// First MFMA of such a chain: C = 0 as an inline constant (no VALU zeroing,
+// so no VALU-write -> MFMA-read wait either); early-clobber output ("=&v"),
+// as an MFMA's D must not overlap its A / B.
+__device__ __forceinline__ void mfma_vq0(f32x16_t& acc, const bf16x8_t& a, bf16x8_t& bq) {
+  asm volatile("v_mfma_f32_32x32x16_bf16 %0, %2, %1, 0" : "=&v"(acc), "+a"(bq) : "v"(a));
+}
+// After the last MFMA of an S / dP chain: the XDL-write -> VALU-read wait
+// states (8-pass 32x32x16: 12) before anything reads the results, and the
+// results redefined behind the nops so no reader is scheduled above them.
+__device__ __forceinline__ void mfma_result_fence(f32x16_t& x) {
+  asm volatile("s_nop 7\n\ts_nop 4" : "+v"(x));
+}
+__device__ __forceinline__ void mfma_result_fence(f32x16_t& x, f32x16_t& y) {
+  asm volatile("s_nop 7\n\ts_nop 4" : "+v"(x), "+v"(y));
 }
 }  // namespace
 

@@ -42,21 +42,9 @@
 #include "attention_common.h"
 
 namespace {
-constexpr int KT = 64;                     // keys per DMA tile (two steps of 32)
-constexpr int QSLOT = 2 * TILE_BYTES;      // K | V image of one tile (32 KiB)
-constexpr int QNSLOT = 4;
-constexpr int QLDS = QNSLOT * QSLOT;       // 128 KiB
-
-// S^T / dP^T chains: accumulator in VGPRs (the VALU reads it), B operand (a
-// Q / dO fragment) pinned in AGPRs ("+a": the AGPR copy is the live value).
-// First of a chain: C = 0 as an inline constant (no VALU zeroing, so no
-// VALU-write -> MFMA-read wait); early-clobber, D must not overlap A / B.
-__device__ __forceinline__ void mq0(f32x16_t& acc, const bf16x8_t& a, bf16x8_t& bq) {
-  asm volatile("v_mfma_f32_32x32x16_bf16 %0, %2, %1, 0" : "=&v"(acc), "+a"(bq) : "v"(a));
-}
-__device__ __forceinline__ void mq(f32x16_t& acc, const bf16x8_t& a, bf16x8_t& bq) {
-  asm volatile("v_mfma_f32_32x32x16_bf16 %0, %2, %1, %0" : "+v"(acc), "+a"(bq) : "v"(a));
-}
+// The MFMA wrappers (S^T / dP^T: mfma_vq0 / mfma_vq on the Q / dO fragments in
+// AGPRs; dQ^T: mfma_a), vm_wait<N> and the K | V ring's geometry (KT = two
+// steps of 32 keys): attention_common.h.
 // the last k-step of phase A: four MFMAs and the XDL-write -> VALU-read wait
 // states (8-pass 32x32x16: 12) in ONE statement, so the allocator cannot
 // copy a result between the MFMA and the nops
@@ -71,10 +59,6 @@ __device__ __forceinline__ void mq4_fenced(f32x16_t& s0, f32x16_t& s1, f32x16_t&
       "s_nop 7\n\ts_nop 4"
       : "+v"(s0), "+v"(s1), "+v"(p0), "+v"(p1), "+a"(q0), "+a"(q1), "+a"(d0), "+a"(d1)
       : "v"(ka), "v"(va));
-}
-// dQ^T accumulation, accumulator pinned to AGPRs
-__device__ __forceinline__ void ma(f32x16_t& acc, const bf16x8_t& a, const bf16x8_t& b) {
-  asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
 }
 // VALU-written dS^T operands -> MFMA read: the wait states, with the operands
 // named so none of them is written behind the nops.  The dQ^T tiles are named
@@ -101,11 +85,6 @@ __device__ __forceinline__ void qd_ready(bf16x8_t (&qf)[2][8], bf16x8_t (&df)[2]
                  "+a"(df[0][5]), "+a"(df[0][6]), "+a"(df[0][7]), "+a"(df[1][0]), "+a"(df[1][1]),
                  "+a"(df[1][2]), "+a"(df[1][3]), "+a"(df[1][4]), "+a"(df[1][5]), "+a"(df[1][6]),
                  "+a"(df[1][7]));
-}
-template <int N>
-__device__ __forceinline__ void vmw() {
-  static_assert(N >= 0 && N < 64, "vmcnt range");
-  __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (15 << 8) | ((N >> 4) << 14));
 }
 __device__ __forceinline__ uint32_t pk2(float lo, float hi) { return mxk::pack2bf(lo, hi); }
 }  // namespace
@@ -137,7 +116,7 @@ mxk_attn_bwd_dq256_kernel(const uint16_t* __restrict__ q, const uint16_t* __rest
                           unsigned long long* __restrict__ stamps = nullptr, int succ = 0,
                           long dq_tok = 0, const float* __restrict__ rcos = nullptr,
                           const float* __restrict__ rsin = nullptr) {
-  __shared__ __attribute__((aligned(16))) char smem[QLDS + 4 * 256];   // ring | prefetch sinks
+  __shared__ __attribute__((aligned(16))) char smem[KV_RING + 4 * 256];   // ring | prefetch sinks
   unsigned long long st_0 = 0, st_c = 0, st_seg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   if constexpr (STAMP) st_0 = st_c = __builtin_readcyclecounter();
   // segment e ends here: 0 prologue (offsets, zeroing), 1 phase A, 2 phase
@@ -196,7 +175,7 @@ mxk_attn_bwd_dq256_kernel(const uint16_t* __restrict__ q, const uint16_t* __rest
   // tests/test_isa_hazards.py's valu_sgpr_to_vmem audits)
   auto issue_piece = [&](int t, int i) {
     const int p = i >> 1;
-    uint32_t d0 = sm32 + ((t + 2) & 3) * QSLOT + (4 * wave + p) * 1024 + (i & 1) * TILE_BYTES;
+    uint32_t d0 = sm32 + ((t + 2) & 3) * KV_SLOT + (4 * wave + p) * 1024 + (i & 1) * TILE_BYTES;
     asm volatile("" : "+s"(d0));
     const uint32_t ch16 = static_cast<uint32_t>((cbase ^ p) << 4);
     const uint32_t voff = (i & 1) ? vrow0 + static_cast<uint32_t>(p * 4 * v_tok * 2) + ch16
@@ -230,7 +209,7 @@ mxk_attn_bwd_dq256_kernel(const uint16_t* __restrict__ q, const uint16_t* __rest
                                 dout + (static_cast<long>(nb) * S + nr0) * tokd + static_cast<long>(nh) * D,
                                 o + (static_cast<long>(nb) * S + nr0) * tokd + static_cast<long>(nh) * D};
     const long strides[3] = {q_tok, tokd, tokd};
-    uint32_t sink = sm32 + QLDS + wave * 256;
+    uint32_t sink = sm32 + KV_RING + wave * 256;
     asm volatile("" : "+s"(sink));
 #pragma unroll
     for (int m = 0; m < 6; ++m) {
@@ -284,7 +263,7 @@ mxk_attn_bwd_dq256_kernel(const uint16_t* __restrict__ q, const uint16_t* __rest
   stage(dorow, tokd, regA);
   stage(orow, tokd, regB);
   stamp(5);
-  vmw<0>();                          // own pieces (no other wave reads them)
+  vm_wait<0>();                      // own pieces (no other wave reads them)
   asm volatile("" : "+v"(lv[0]), "+v"(lv[1]) :: "memory");
   int koff[8];
 #pragma unroll
@@ -323,7 +302,7 @@ mxk_attn_bwd_dq256_kernel(const uint16_t* __restrict__ q, const uint16_t* __rest
   issue(0);
   issue(1);
   // Q (own) landed: 16 pieces of tiles 0 / 1 and the two rowc stores may fly
-  vmw<18>();
+  vm_wait<18>();
 #pragma unroll
   for (int g = 0; g < 2; ++g)
 #pragma unroll
@@ -331,7 +310,7 @@ mxk_attn_bwd_dq256_kernel(const uint16_t* __restrict__ q, const uint16_t* __rest
   // Q read (tile 2 goes into slot 0 during tile 0) and tile 0 landed
   // (tile 1's 8 may fly; the rowc stores are older than tile 0)
   __builtin_amdgcn_s_waitcnt(0xC07F);
-  vmw<8>();
+  vm_wait<8>();
   __builtin_amdgcn_s_barrier();
   stamp(7);
 
@@ -447,28 +426,28 @@ mxk_attn_bwd_dq256_kernel(const uint16_t* __restrict__ q, const uint16_t* __rest
         pre_b1 = kread(nextb, 1);
       }
       if (s == 0) {
-        mq0(sacc[PA][0], ka, qf[0][0]);
+        mfma_vq0(sacc[PA][0], ka, qf[0][0]);
         beside();
         __builtin_amdgcn_sched_barrier(0);
-        mq0(sacc[PA][1], ka, qf[1][0]);
+        mfma_vq0(sacc[PA][1], ka, qf[1][0]);
         beside();
         __builtin_amdgcn_sched_barrier(0);
-        mq0(pacc[PA][0], va, df[0][0]);
+        mfma_vq0(pacc[PA][0], va, df[0][0]);
         beside();
         __builtin_amdgcn_sched_barrier(0);
-        mq0(pacc[PA][1], va, df[1][0]);
+        mfma_vq0(pacc[PA][1], va, df[1][0]);
         beside();
       } else if (s < 7) {
-        mq(sacc[PA][0], ka, qf[0][s]);
+        mfma_vq(sacc[PA][0], ka, qf[0][s]);
         beside();
         __builtin_amdgcn_sched_barrier(0);
-        mq(sacc[PA][1], ka, qf[1][s]);
+        mfma_vq(sacc[PA][1], ka, qf[1][s]);
         beside();
         __builtin_amdgcn_sched_barrier(0);
-        mq(pacc[PA][0], va, df[0][s]);
+        mfma_vq(pacc[PA][0], va, df[0][s]);
         beside();
         __builtin_amdgcn_sched_barrier(0);
-        mq(pacc[PA][1], va, df[1][s]);
+        mfma_vq(pacc[PA][1], va, df[1][s]);
         beside();
       } else {
         mq4_fenced(sacc[PA][0], sacc[PA][1], pacc[PA][0], pacc[PA][1], qf[0][7], qf[1][7],
@@ -504,10 +483,10 @@ mxk_attn_bwd_dq256_kernel(const uint16_t* __restrict__ q, const uint16_t* __rest
         pre_k = lds_b128(nexta + koff[0]);
         pre_v = lds_b128(nexta + TILE_BYTES + koff[0]);
       }
-      ma(dqa[0][i >> 1], a, dsf[PB][0][i & 1]);
+      mfma_a(dqa[0][i >> 1], a, dsf[PB][0][i & 1]);
       if (SOFT) smi(cur{}, 0, 3 * i, lim, mask_c);
       __builtin_amdgcn_sched_barrier(0);
-      ma(dqa[1][i >> 1], a, dsf[PB][1][i & 1]);
+      mfma_a(dqa[1][i >> 1], a, dsf[PB][1][i & 1]);
       if (SOFT) {
         smi(cur{}, 0, 3 * i + 1, lim, mask_c);
         smi(cur{}, 0, 3 * i + 2, lim, mask_c);
@@ -524,8 +503,8 @@ mxk_attn_bwd_dq256_kernel(const uint16_t* __restrict__ q, const uint16_t* __rest
     using F = std::false_type;
     using P0 = std::integral_constant<int, 0>;
     using P1 = std::integral_constant<int, 1>;
-    const char* cur = smem + ((t + 2) & 3) * QSLOT;
-    const char* prv = t ? smem + ((t + 1) & 3) * QSLOT : cur;
+    const char* cur = smem + ((t + 2) & 3) * KV_SLOT;
+    const char* prv = t ? smem + ((t + 1) & 3) * KV_SLOT : cur;
     // step 2t: A(2t) beside softmax(2t-1, g1) (never diagonal); B(2t-1)
     // beside softmax(2t, g0)
     using T_ = std::true_type;
@@ -553,7 +532,7 @@ mxk_attn_bwd_dq256_kernel(const uint16_t* __restrict__ q, const uint16_t* __rest
                    "+a"(dqa[1][0]), "+a"(dqa[1][1]), "+a"(dqa[1][2]), "+a"(dqa[1][3]));
     // barrier: tile t+1 landed (own pieces; tile t+2's 8 may fly) and
     // every wave past B(2t-1), the last reader of tile t-1's slot
-    vmw<8>();
+    vm_wait<8>();
     __builtin_amdgcn_s_barrier();
     stamp(3);
   };
@@ -565,7 +544,7 @@ mxk_attn_bwd_dq256_kernel(const uint16_t* __restrict__ q, const uint16_t* __rest
   {
     const int j = 2 * T - 1;
     const int lim = lim_of(j, 1);
-    const char* kt = smem + ((T + 1) & 3) * QSLOT + 32 * 256;
+    const char* kt = smem + ((T + 1) & 3) * KV_SLOT + 32 * 256;
     pre_b0 = kread(kt, 0);
     pre_b1 = kread(kt, 1);
 #pragma unroll
@@ -577,7 +556,7 @@ mxk_attn_bwd_dq256_kernel(const uint16_t* __restrict__ q, const uint16_t* __rest
   }
   // the DMA of tiles past the block (T and T + 1) must land before the
   // workgroup ends and its LDS goes to another one
-  vmw<0>();
+  vm_wait<0>();
   // dQ^T final: drain the asm MFMAs before the accumulators are read
   asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" ::: "memory");
 #pragma unroll
@@ -626,7 +605,7 @@ mxk_attn_bwd_dq256_kernel(const uint16_t* __restrict__ q, const uint16_t* __rest
       }
   __builtin_amdgcn_s_waitcnt(0xC07F);   // own image: no other wave reads it
   if constexpr (ROPE) {
-    vmw<0>();                            // the table pieces, every wave's
+    vm_wait<0>();                        // the table pieces, every wave's
     __builtin_amdgcn_s_barrier();
   }
   // lane l: chunk l & 15 of rows (l >> 4) + 4 i

@@ -325,7 +325,7 @@ mxk_attn_fwd_dma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restri
 #pragma unroll
   for (int s = 0; s < 8; ++s) asm volatile("" ::"v"(qf[s]));
   if constexpr (DOC) asm volatile("" ::"v"(ds_row));
-  vm_wait0();   // tile 0 (DOC: tile j_lo)
+  vm_wait<0>();   // tile 0 (DOC: tile j_lo)
   __syncthreads();
 
   // the loop body; UNROLL makes the LDS buffer a compile-time constant (read
@@ -506,7 +506,7 @@ mxk_attn_fwd_dma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restri
     }
     // tile j+1 (own pieces) landed; the barrier publishes every wave's pieces
     // and certifies that buffer buf is no longer read
-    vm_wait0();
+    vm_wait<0>();
     __syncthreads();
   };
   if constexpr (UNROLL) {

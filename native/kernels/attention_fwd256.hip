@@ -39,46 +39,9 @@
 #include "attention_common.h"
 
 namespace {
-constexpr int KT = 64;                         // keys per tile
-constexpr int FSLOT = 2 * TILE_BYTES;          // K | V image of one tile (32 KiB)
-constexpr int FNSLOT = 4;
-constexpr int FLDS = FNSLOT * FSLOT;           // 128 KiB
-
-// MFMA with a VGPR accumulator (S^T): FENCE for the first of a chain whose
-// C / operands a VALU instruction may just have written
-template <bool FENCE = false>
-__device__ __forceinline__ void fmfma_v(f32x16_t& acc, const bf16x8_t& a, const bf16x8_t& b) {
-  if constexpr (FENCE)
-    asm volatile("s_nop 2\n\tv_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
-  else
-    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
-}
-// S^T chain with the B operand (Q^T fragment) held in AGPRs: the 64
-// registers of both groups' Q live in the accumulator file for the whole
-// kernel, beside O^T, leaving the arch VGPRs to S^T, P^T and the operands
-template <bool FENCE = false>
-__device__ __forceinline__ void fmfma_vq(f32x16_t& acc, const bf16x8_t& a, bf16x8_t& bq) {
-  // "+a" on the Q fragment: the AGPR copy is the live value (an "a" input
-  // alone lets the allocator keep Q in VGPRs and copy it in per MFMA)
-  if constexpr (FENCE)
-    asm volatile("s_nop 2\n\tv_mfma_f32_32x32x16_bf16 %0, %2, %1, %0" : "+v"(acc), "+a"(bq) : "v"(a));
-  else
-    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %2, %1, %0" : "+v"(acc), "+a"(bq) : "v"(a));
-}
-// first MFMA of an S^T chain: C = 0 as an inline constant (no VALU
-// zeroing, so no VALU-write -> MFMA wait either); early-clobber output, as
-// an MFMA's D must not overlap its A / B
-__device__ __forceinline__ void fmfma_vq0(f32x16_t& acc, const bf16x8_t& a, bf16x8_t& bq) {
-  asm volatile("v_mfma_f32_32x32x16_bf16 %0, %2, %1, 0" : "=&v"(acc), "+a"(bq) : "v"(a));
-}
-// MFMA with the accumulator pinned to AGPRs (O^T)
-__device__ __forceinline__ void fmfma_a(f32x16_t& acc, const bf16x8_t& a, const bf16x8_t& b) {
-  asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
-}
-// 8-pass XDL write -> VALU read: 12 wait states, results redefined behind them
-__device__ __forceinline__ void ffence2(f32x16_t& x, f32x16_t& y) {
-  asm volatile("s_nop 7\n\ts_nop 4" : "+v"(x), "+v"(y));
-}
+// The MFMA wrappers (S^T: mfma_vq0 / mfma_vq on the Q^T fragments in AGPRs;
+// O^T: mfma_a), mfma_result_fence, vm_wait<N> and the K | V ring's geometry:
+// attention_common.h.
 // VALU-written MFMA operands (P^T) and accumulators (a rescaled O^T) ->
 // MFMA read: the wait states, with both named so nothing of either is
 // written behind the nops
@@ -102,7 +65,6 @@ __device__ __forceinline__ void agpr_scale16(f32x16_t& x, float a) {
                : "v"(a));
 }
 #undef MXK_AS1
-__device__ __forceinline__ void vm_wait_n8() { __builtin_amdgcn_s_waitcnt(8 | (7 << 4) | (15 << 8)); }
 }  // namespace
 
 // STAMP (diagnostic build, mxk_attn_fwd256_stamps): each wave adds up the
@@ -116,7 +78,7 @@ mxk_attn_fwd256_kernel(const uint16_t* __restrict__ q, const uint16_t* __restric
                        const uint16_t* __restrict__ v, uint16_t* __restrict__ o,
                        float* __restrict__ lse, int S, int Hq, int Hkv, long q_tok, long k_tok,
                        long v_tok, float scale, unsigned long long* __restrict__ stamps = nullptr) {
-  __shared__ __attribute__((aligned(16))) char smem[FLDS];
+  __shared__ __attribute__((aligned(16))) char smem[KV_RING];
   unsigned long long st_p1 = 0, st_p2 = 0, st_bar = 0, st_0 = 0, st_pro = 0, st_tail = 0;
   if constexpr (STAMP) st_0 = __builtin_readcyclecounter();
   const int tid = threadIdx.x;
@@ -154,7 +116,7 @@ mxk_attn_fwd256_kernel(const uint16_t* __restrict__ q, const uint16_t* __restric
   const uint32_t sm32 = mxk::lds_addr32(smem);
   // piece p (0..3) of tile j: one K and one V LDS-DMA instruction
   auto issue_piece = [&](int j, int p) {
-    uint32_t d0 = sm32 + (j % FNSLOT) * FSLOT + (4 * wave + p) * 1024;
+    uint32_t d0 = sm32 + (j % KV_NSLOT) * KV_SLOT + (4 * wave + p) * 1024;
     // opaque base: the piece addresses are one s_add each here, not 32
     // loop-invariant SGPRs (4 slots x 8 pieces) hoisted and spilled
     asm volatile("" : "+s"(d0));
@@ -251,17 +213,17 @@ mxk_attn_fwd256_kernel(const uint16_t* __restrict__ q, const uint16_t* __restric
       for (int u = 0; u < 4; ++u) {
         const int g = u >> 1, kh = u & 1;
         if (s == 0)   // C = 0: no VALU zeroing of S^T
-          fmfma_vq0(sacc[B][g][kh], a[kh], qf[g][s]);
+          mfma_vq0(sacc[B][g][kh], a[kh], qf[g][s]);
         else
-          fmfma_vq(sacc[B][g][kh], a[kh], qf[g][s]);
+          mfma_vq(sacc[B][g][kh], a[kh], qf[g][s]);
         beside(4 * s + u);
         __builtin_amdgcn_sched_barrier(0);
       }
       a[0] = n[0];
       a[1] = n[1];
     }
-    ffence2(sacc[B][0][0], sacc[B][0][1]);
-    ffence2(sacc[B][1][0], sacc[B][1][1]);
+    mfma_result_fence(sacc[B][0][0], sacc[B][0][1]);
+    mfma_result_fence(sacc[B][1][0], sacc[B][1][1]);
     __builtin_amdgcn_sched_barrier(0);
   };
   auto vread = [&](const char* vt, int i) {
@@ -279,7 +241,7 @@ mxk_attn_fwd256_kernel(const uint16_t* __restrict__ q, const uint16_t* __restric
       const bf16x8_t n = i < 15 ? vread(vt, i + 1) : a;
 #pragma unroll
       for (int g = 0; g < 2; ++g) {
-        fmfma_a(oacc[g][i >> 2], a, pf[B][g][i & 3]);
+        mfma_a(oacc[g][i >> 2], a, pf[B][g][i & 3]);
         beside(2 * i + g);
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -376,8 +338,8 @@ mxk_attn_fwd256_kernel(const uint16_t* __restrict__ q, const uint16_t* __restric
   // (Spreading the 8 DMA instructions over phase 1 instead, one per 4
   // MFMAs, measured +1030 cycles in phase 1 against -430 here.)
   auto barrier_j = [&](int j) {
-    if (j + 2 < J) vm_wait_n8();
-    else vm_wait0();
+    if (j + 2 < J) vm_wait<8>();
+    else vm_wait<0>();
     __builtin_amdgcn_s_barrier();
     if (j + 3 < J) issue(j + 3);
   };
@@ -394,16 +356,16 @@ mxk_attn_fwd256_kernel(const uint16_t* __restrict__ q, const uint16_t* __restric
     pf[1][g][1] = bf16x8_t{};
   }
   {
-    uint4* z = reinterpret_cast<uint4*>(smem + 3 * FSLOT + TILE_BYTES);
+    uint4* z = reinterpret_cast<uint4*>(smem + 3 * KV_SLOT + TILE_BYTES);
 #pragma unroll
     for (int i = 0; i < 4; ++i) z[tid + 256 * i] = make_uint4(0, 0, 0, 0);
     __syncthreads();
   }
   auto tile = [&](int j, auto slot_c, auto mask_c) {
     constexpr int SL = decltype(slot_c)::value;        // == j % 4
-    constexpr int PSL = (SL + FNSLOT - 1) % FNSLOT;    // tile j-1's slot
-    const char* tj = smem + SL * FSLOT;
-    const char* tp = smem + PSL * FSLOT;
+    constexpr int PSL = (SL + KV_NSLOT - 1) % KV_NSLOT;    // tile j-1's slot
+    const char* tj = smem + SL * KV_SLOT;
+    const char* tp = smem + PSL * KV_SLOT;
     using cur = std::integral_constant<int, SL & 1>;
     using prv = std::integral_constant<int, (SL & 1) ^ 1>;
     // phase 1: S^T(j) beside the finish of softmax(j-1)
@@ -454,7 +416,7 @@ mxk_attn_fwd256_kernel(const uint16_t* __restrict__ q, const uint16_t* __restric
 #pragma unroll
   for (int u = 0; u < 32; ++u) finish(std::integral_constant<int, 1>{}, u);
   __builtin_amdgcn_sched_barrier(0);
-  pv2(std::integral_constant<int, 1>{}, smem + 3 * FSLOT, [](int) {});
+  pv2(std::integral_constant<int, 1>{}, smem + 3 * KV_SLOT, [](int) {});
   if constexpr (STAMP) st_tail = __builtin_readcyclecounter() - st_0;
   // O accumulators final: drain the asm MFMAs before reading them
   asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" ::: "memory");

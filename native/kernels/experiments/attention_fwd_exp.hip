@@ -126,7 +126,7 @@ mxk_attn_fwd_pp_kernel(const uint16_t* __restrict__ q, const uint16_t* __restric
 
 #pragma unroll
   for (int s = 0; s < 8; ++s) asm volatile("" ::"v"(qf[s]));
-  vm_wait0();   // Q, K_0, V_0, K_1
+  vm_wait<0>();   // Q, K_0, V_0, K_1
   __syncthreads();
 
   // tile j is active for this wave unless all its rows precede key 64 j;

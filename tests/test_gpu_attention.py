@@ -106,6 +106,17 @@ def test_attn_bwd_variants_into_strided_dkdv(cuda_device, B, S, Hq, Hkv, causal,
         ref5 = A.attn_bwd(q, k, v, o, lse, dout, causal=causal, variant=5)
         for a3, a5 in zip(ref3, ref5):
             assert (a3.float() - a5.float()).abs().max().item() <= 1e-2 * max(1.0, a3.float().abs().max().item())
+    if variant == 4 and S == 384:
+        # the dQ walk unrolled by two against the plain one (attention_plan.h:
+        # bit-identical): S 384 has query blocks of 1, 2 and 3 key tiles, the
+        # odd and even tile counts of a two-tile trip
+        q4, k4, v4 = _qkv(1, 384, 4, 2, cuda_device, seed=3, fused=True)
+        o4, lse4 = A.attn_fwd(q4, k4, v4, causal=True)
+        dout4 = torch.randn(1, 384, 4, 128, device=cuda_device, generator=g).bfloat16()
+        ref3 = A.attn_bwd(q4, k4, v4, o4, lse4, dout4, causal=True, variant=3)
+        got4 = A.attn_bwd(q4, k4, v4, o4, lse4, dout4, causal=True, variant=4)
+        for name, a3, a4 in zip(("dq", "dk", "dv"), ref3, got4):
+            assert torch.equal(a3, a4), name
 
 
 @pytest.mark.parametrize("B,S,Hq,Hkv,causal", [
