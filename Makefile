@@ -14,6 +14,7 @@
 #   make test-gemm-plan       the bf16 GEMM plans' sweep, hostile integers included (host, ASan+UBSan build)
 #   make test-attention-doc   the document-mask predicate and tile bounds (host, ASan+UBSan build)
 #   make test-mxfp4-format    the e2m1 conversion and block exponent over every bf16 (host, ASan+UBSan build)
+#   make test-mxfp4-sr        Philox4x32-10, the non-clipping block exponent and the stochastic e2m1 rounding over every bf16 (host, ASan+UBSan build)
 #   make test-gemm-bench-report  mx-gemm-bench's RESULT lines, pass rule and spot block (host, ASan+UBSan build)
 #
 # Everything lands inside the repo so `gpurun` snapshots carry it to the box.
@@ -34,7 +35,8 @@ LDLIBS_NODE := -ldl -lpthread
 KERNEL_SRCS := native/kernels/gemm_bf16.hip native/kernels/vector_add.hip \
                native/kernels/fused_ops.hip native/kernels/optim.hip native/kernels/attention_fwd.hip native/kernels/attention_bwd.hip native/kernels/attention_bwd256.hip native/kernels/attention_fwd256.hip native/kernels/attention_dq256.hip \
                native/kernels/gemm_bf16_layouts.hip native/kernels/xent.hip native/kernels/contention.hip \
-               native/kernels/gemm_mxfp8.hip native/kernels/gemm_mxfp4.hip
+               native/kernels/gemm_mxfp8.hip native/kernels/gemm_mxfp4.hip \
+               native/kernels/quantize_mxfp4_sr.hip
 KERNEL_OBJS := $(patsubst native/kernels/%.hip,$(BUILD)/kernels/%.o,$(KERNEL_SRCS))
 EXP_SRCS    := $(KERNEL_SRCS) $(wildcard native/kernels/experiments/*.hip)
 EXP_OBJS    := $(patsubst native/kernels/%.hip,$(BUILD)/exp/%.o,$(EXP_SRCS))
@@ -44,7 +46,7 @@ NODE_SRCS := $(wildcard native/libmxnode/*.cc)
 NODE_OBJS := $(patsubst native/libmxnode/%.cc,$(BUILD)/node/%.o,$(NODE_SRCS))
 NODE_HDRS := $(wildcard native/libmxnode/*.h)
 
-.PHONY: all kernels gemm-exp node tools clean test-native test-native-tsan test-attention-plan test-gemm-plan test-attention-doc test-mxfp4-format test-gemm-bench-report fake-amdsmi
+.PHONY: all kernels gemm-exp node tools clean test-native test-native-tsan test-attention-plan test-gemm-plan test-attention-doc test-mxfp4-format test-mxfp4-sr test-gemm-bench-report fake-amdsmi
 all: kernels node tools fake-amdsmi
 
 kernels: $(OUT_LIB)/libmxkernels.so
@@ -169,6 +171,14 @@ test-mxfp4-format: $(BUILD)/asan/mxfp4_format_sweep
 	$<
 
 $(BUILD)/asan/mxfp4_format_sweep: native/kernels/tests/mxfp4_format_sweep.cc native/kernels/mxfp4_format.h
+	@mkdir -p $(dir $@)
+	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -Wshadow -fsanitize=address,undefined -fno-sanitize-recover=all \
+	    -fno-omit-frame-pointer -Inative/kernels -o $@ $<
+
+test-mxfp4-sr: $(BUILD)/asan/mxfp4_sr_sweep
+	$<
+
+$(BUILD)/asan/mxfp4_sr_sweep: native/kernels/tests/mxfp4_sr_sweep.cc native/kernels/mxfp4_format.h native/kernels/mx_philox.h
 	@mkdir -p $(dir $@)
 	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -Wshadow -fsanitize=address,undefined -fno-sanitize-recover=all \
 	    -fno-omit-frame-pointer -Inative/kernels -o $@ $<

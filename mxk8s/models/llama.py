@@ -29,7 +29,7 @@ import torch.nn.functional as F
 
 from ..ops.attention import (flash_attention, proj_rope_attention, qkv_rope_attention,
                               supported as flash_supported)
-from ..ops.linear import Linear, SwiGLULinear, swiglu_mlp
+from ..ops.linear import GRAD_ROUNDINGS, Linear, SwiGLULinear, swiglu_mlp
 from ..ops.xent import cross_entropy
 from ..ops.embedding import Embedding
 from ..ops.fused import add_rmsnorm, qkv_rope, rmsnorm, rope_tables
@@ -51,10 +51,20 @@ class LlamaConfig:
     # without the fused RoPE / SwiGLU epilogues, which are bf16 kernels; lm_head
     # and everything that is not a linear layer stay bf16
     linear_dtype: str = "bf16"
+    # "stochastic" (opt-in, with linear_dtype "mxfp4"): those four layers
+    # quantise their output gradient with stochastic rounding
+    # (mxk8s.ops.linear.linear_mxfp4, grad_rounding)
+    grad_rounding: str = "nearest"
 
     def __post_init__(self):
         if self.linear_dtype not in Linear.COMPUTE:
             raise ValueError(f"linear_dtype must be one of {Linear.COMPUTE}, "
+                             f"got {self.linear_dtype!r}")
+        if self.grad_rounding not in GRAD_ROUNDINGS:
+            raise ValueError(f"grad_rounding must be one of {GRAD_ROUNDINGS}, "
+                             f"got {self.grad_rounding!r}")
+        if self.grad_rounding != "nearest" and self.linear_dtype != "mxfp4":
+            raise ValueError(f"grad_rounding={self.grad_rounding!r} needs linear_dtype=\"mxfp4\", "
                              f"got {self.linear_dtype!r}")
 
     @classmethod
@@ -107,8 +117,9 @@ class Attention(nn.Module):
         super().__init__()
         self.cfg = cfg
         hd = cfg.head_dim
-        self.wqkv = Linear(cfg.dim, (cfg.n_heads + 2 * cfg.n_kv_heads) * hd, compute=cfg.linear_dtype)
-        self.wo = Linear(cfg.n_heads * hd, cfg.dim, compute=cfg.linear_dtype)
+        mx = dict(compute=cfg.linear_dtype, grad_rounding=cfg.grad_rounding)
+        self.wqkv = Linear(cfg.dim, (cfg.n_heads + 2 * cfg.n_kv_heads) * hd, **mx)
+        self.wo = Linear(cfg.n_heads * hd, cfg.dim, **mx)
 
     def forward(self, x, cos, sin, doc=None):
         B, S, _ = x.shape
@@ -155,10 +166,11 @@ class MLP(nn.Module):
     def __init__(self, cfg: LlamaConfig):
         super().__init__()
         self.bf16_linears = cfg.linear_dtype == "bf16"
-        self.w13 = Linear(cfg.dim, 2 * cfg.ffn_dim, compute=cfg.linear_dtype)   # [gate | up]
+        mx = dict(compute=cfg.linear_dtype, grad_rounding=cfg.grad_rounding)
+        self.w13 = Linear(cfg.dim, 2 * cfg.ffn_dim, **mx)   # [gate | up]
         # w2(swiglu(.)) as one node: the SwiGLU backward runs in the epilogue
         # of w2's input-gradient GEMM
-        self.w2 = SwiGLULinear(cfg.ffn_dim, cfg.dim, compute=cfg.linear_dtype)
+        self.w2 = SwiGLULinear(cfg.ffn_dim, cfg.dim, **mx)
 
     def forward(self, x):
         if x.is_cuda and x.dtype == torch.bfloat16 and self.bf16_linears:

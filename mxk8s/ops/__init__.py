@@ -8,7 +8,10 @@
 * :func:`quantize_mxfp4`, :func:`gemm_mxfp4_tn` — MXFP4 (block-scaled e2m1, two codes per
   byte) quantiser and scaled-MFMA GEMM (validator config 3, ``--gemm-dtypes mxfp4``);
   :func:`quantize_mxfp4_t`, :func:`quantize_mxfp4_dual` — the transposing quantiser,
-  :func:`linear_mxfp4` — a linear layer's three products on that GEMM (opt-in)
+  :func:`linear_mxfp4` — a linear layer's three products on that GEMM (opt-in);
+  ``rounding="stochastic"`` on the quantisers and ``grad_rounding="stochastic"`` on the
+  layer round the output gradient stochastically, seeds from :func:`sr_reseed` /
+  :func:`sr_next`
 * :func:`vector_add`    — smoke-test payload (config 2)
 * :func:`rmsnorm`, :func:`swiglu`, :func:`rope` — fused training ops (config 5)
 """
@@ -16,7 +19,7 @@ from .gemm import gemm_bf16_tn, gemm_flops, is_fast_shape
 from .mxfp8 import (quantize_mxfp8, quantize_mxfp8_ref, quantize_mxfp8_t, quantize_mxfp8_dual,
                     dequantize_mxfp8, gemm_mxfp8_tn, is_fast_shape_mxfp8)
 from .mxfp4 import (quantize_mxfp4, quantize_mxfp4_ref, quantize_mxfp4_t, quantize_mxfp4_dual,
-                    dequantize_mxfp4, gemm_mxfp4_tn, is_fast_shape_mxfp4)
+                    dequantize_mxfp4, gemm_mxfp4_tn, is_fast_shape_mxfp4, sr_reseed, sr_next)
 from .linear import linear_mxfp8, is_mxfp8_linear_shape, linear_mxfp4, is_mxfp4_linear_shape
 from .vector_add import vector_add
 from .fused import rmsnorm, swiglu, rope, rope_tables
@@ -27,4 +30,4 @@ __all__ = ["gemm_bf16_tn", "gemm_flops", "is_fast_shape", "quantize_mxfp8", "qua
            "dequantize_mxfp8", "gemm_mxfp8_tn", "is_fast_shape_mxfp8", "quantize_mxfp4",
            "quantize_mxfp4_ref", "quantize_mxfp4_t", "quantize_mxfp4_dual", "linear_mxfp4",
            "is_mxfp4_linear_shape", "dequantize_mxfp4", "gemm_mxfp4_tn", "is_fast_shape_mxfp4",
-           "vector_add", "rmsnorm", "swiglu", "rope", "rope_tables", "kernels_available", "KERNEL_LIB_PATH"]
+           "sr_reseed", "sr_next", "vector_add", "rmsnorm", "swiglu", "rope", "rope_tables", "kernels_available", "KERNEL_LIB_PATH"]

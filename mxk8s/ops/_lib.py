@@ -25,6 +25,7 @@ _lib = None
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
 _l = ctypes.c_long
+_u64 = ctypes.c_uint64
 _f = ctypes.c_float
 _fp = ctypes.POINTER(ctypes.c_float)
 
@@ -61,6 +62,10 @@ _SIGNATURES = {
     "mxk_quantize_mxfp4": (_i, [_vp, _vp, _vp, _l, _i, _l, _l, _l, _vp]),
     "mxk_quantize_mxfp4_t": (_i, [_vp, _vp, _vp, _l, _l, _l, _l, _l, _vp]),
     "mxk_quantize_mxfp4_dual": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _l, _vp]),
+    # stochastic rounding (quantize_mxfp4_sr.hip): the seed before the stream
+    "mxk_quantize_mxfp4_sr": (_i, [_vp, _vp, _vp, _l, _i, _l, _l, _l, _u64, _vp]),
+    "mxk_quantize_mxfp4_sr_t": (_i, [_vp, _vp, _vp, _l, _l, _l, _l, _l, _u64, _vp]),
+    "mxk_quantize_mxfp4_sr_dual": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _l, _u64, _vp]),
     "mxk_gemm_bf16_ex": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "mxk_gemm_bf16_ex_variant": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "mxk_gemm_bf16_ex_ws": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _l,

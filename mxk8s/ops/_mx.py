@@ -59,48 +59,64 @@ def _images(x: torch.Tensor, per_byte: int, dtype: torch.dtype, transposed: bool
             torch.empty((R, C // BLOCK), dtype=torch.uint8, device=x.device))
 
 
-def quantize_rows(name: str, per_byte: int, dtype: torch.dtype, ref: Callable, x: torch.Tensor):
+def _sr(seed):
+    """(entry-point infix, reference arguments, arguments before the stream) of
+    a quantiser call: nearest rounding for ``seed`` None, else stochastic
+    rounding with that seed (the entry points ``mxk_quantize_<name>_sr*``)."""
+    return ("", (), ()) if seed is None else ("_sr", ("stochastic", seed), (seed,))
+
+
+def quantize_rows(name: str, per_byte: int, dtype: torch.dtype, ref: Callable, x: torch.Tensor,
+                  seed: int | None = None):
     """``quantize_<name>``: ``per_byte`` codes in each ``dtype`` item of ``q``,
     ``ref`` the format's pure-torch quantiser, the kernel ``mxk_quantize_<name>``."""
     check_x(x)
+    sr, ref_args, seed_arg = _sr(seed)
     if x.device.type == "cpu":
-        return ref(x)
+        return ref(x, *ref_args)
     R, K = x.shape
     q, s = _images(x, per_byte, dtype, False)
-    fn = f"mxk_quantize_{name}"
+    fn = f"mxk_quantize_{name}{sr}"
     rc = getattr(_lib.lib(), fn)(x.data_ptr(), q.data_ptr(), s.data_ptr(), R, K, x.stride(0),
-                                 q.stride(0), s.stride(0), _lib.stream_ptr(x.device))
+                                 q.stride(0), s.stride(0), *seed_arg, _lib.stream_ptr(x.device))
     _lib.check(rc, fn)
     return q, s
 
 
-def quantize_t(name: str, per_byte: int, dtype: torch.dtype, ref: Callable, x: torch.Tensor):
+def quantize_t(name: str, per_byte: int, dtype: torch.dtype, ref: Callable, x: torch.Tensor,
+               seed: int | None = None):
     """``quantize_<name>_t``: the images of ``x.t()``; the kernel ``mxk_quantize_<name>_t``."""
     check_xt(x, dual=False)
+    sr, ref_args, seed_arg = _sr(seed)
     if x.device.type == "cpu":
-        return ref(x.t().contiguous())
+        return ref(x.t().contiguous(), *ref_args)
     R, C = x.shape
     qt, st = _images(x, per_byte, dtype, True)
-    fn = f"mxk_quantize_{name}_t"
+    fn = f"mxk_quantize_{name}{sr}_t"
     rc = getattr(_lib.lib(), fn)(x.data_ptr(), qt.data_ptr(), st.data_ptr(), R, C, x.stride(0),
-                                 qt.stride(0), st.stride(0), _lib.stream_ptr(x.device))
+                                 qt.stride(0), st.stride(0), *seed_arg, _lib.stream_ptr(x.device))
     _lib.check(rc, fn)
     return qt, st
 
 
-def quantize_dual(name: str, per_byte: int, dtype: torch.dtype, ref: Callable, x: torch.Tensor):
+def quantize_dual(name: str, per_byte: int, dtype: torch.dtype, ref: Callable, x: torch.Tensor,
+                  seed: int | None = None):
     """``quantize_<name>_dual``: both images from one read of ``x``; the kernel
-    ``mxk_quantize_<name>_dual``."""
+    ``mxk_quantize_<name>_dual``.  Stochastic: the transposed image draws with
+    ``seed + 1`` (mod 2^64)."""
     check_xt(x, dual=True)
+    sr, ref_args, seed_arg = _sr(seed)
     if x.device.type == "cpu":
-        return ref(x) + ref(x.t().contiguous())
+        if seed is None:
+            return ref(x) + ref(x.t().contiguous())
+        return ref(x, *ref_args) + ref(x.t().contiguous(), "stochastic", (seed + 1) % 2 ** 64)
     R, C = x.shape
     q, s = _images(x, per_byte, dtype, False)
     qt, st = _images(x, per_byte, dtype, True)
-    fn = f"mxk_quantize_{name}_dual"
+    fn = f"mxk_quantize_{name}{sr}_dual"
     rc = getattr(_lib.lib(), fn)(x.data_ptr(), q.data_ptr(), s.data_ptr(), qt.data_ptr(), st.data_ptr(),
                                  R, C, x.stride(0), q.stride(0), s.stride(0), qt.stride(0),
-                                 st.stride(0), _lib.stream_ptr(x.device))
+                                 st.stride(0), *seed_arg, _lib.stream_ptr(x.device))
     _lib.check(rc, fn)
     return q, s, qt, st
 

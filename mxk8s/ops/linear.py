@@ -171,6 +171,17 @@ def _mx_weight_grad(weight: torch.Tensor, dyt, xt, gemm):
     return None
 
 
+GRAD_ROUNDINGS = ("nearest", "stochastic")
+
+
+def _check_grad_rounding(grad_rounding, seed=None) -> None:
+    from .mxfp4 import check_rounding
+    if grad_rounding not in GRAD_ROUNDINGS:
+        raise ValueError(f"grad_rounding must be one of {GRAD_ROUNDINGS}, got {grad_rounding!r}")
+    if seed is not None:
+        check_rounding(grad_rounding, seed)
+
+
 def _mx_forward(fmt: str, ctx, x, weight):
     gemm, quantize, _, _ = _mx_ops(fmt)
     ctx.save_for_backward(x, weight)          # bf16, as _LinearFn: no quantised copy is held
@@ -179,12 +190,22 @@ def _mx_forward(fmt: str, ctx, x, weight):
     return y.to(x.dtype).view(*x.shape[:-1], weight.shape[0])
 
 
-def _mx_backward(fmt: str, ctx, dy):
+def _mx_backward(fmt: str, ctx, dy, sr_seed=None):
+    """sr_seed (MXFP4): dy is quantised with stochastic rounding, its row image
+    with this seed and its transposed image with the next one, whichever of
+    the two a call needs; W^T and x^T stay round-to-nearest."""
     gemm, quantize, quantize_t, quantize_dual = _mx_ops(fmt)
     x, weight = ctx.saved_tensors
-    need_x, need_w = ctx.needs_input_grad
+    need_x, need_w = ctx.needs_input_grad[:2]
     dy2 = _bf16_rows(dy.reshape(-1, dy.shape[-1]))
-    if need_x and need_w:
+    if sr_seed is not None:
+        if need_x and need_w:
+            dq, ds, dqt, dst = quantize_dual(dy2, "stochastic", sr_seed)
+        elif need_x:
+            dq, ds = quantize(dy2, "stochastic", sr_seed)
+        elif need_w:
+            dqt, dst = quantize_t(dy2, "stochastic", (sr_seed + 1) % 2 ** 64)
+    elif need_x and need_w:
         dq, ds, dqt, dst = quantize_dual(dy2)
     elif need_x:
         dq, ds = quantize(dy2)
@@ -220,7 +241,26 @@ class _LinearMxfp4Fn(torch.autograd.Function):
         return _mx_backward("mxfp4", ctx, dy)
 
 
-def _mx_linear(name: str, fn, x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
+class _LinearMxfp4SrFn(torch.autograd.Function):
+    """_LinearMxfp4Fn whose backward quantises dy with stochastic rounding.  The
+    seed is fixed at forward time: the explicit one, else the next of the seed
+    source (mxfp4.sr_next), which follows the order of the module calls and not
+    the autograd engine's."""
+
+    @staticmethod
+    def forward(ctx, x, weight, seed):
+        if seed is None:
+            from .mxfp4 import sr_next
+            seed = sr_next()
+        ctx.sr_seed = seed
+        return _mx_forward("mxfp4", ctx, x, weight)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return (*_mx_backward("mxfp4", ctx, dy, ctx.sr_seed), None)
+
+
+def _mx_linear(name: str, fn, x: torch.Tensor, weight: torch.Tensor, *extra) -> torch.Tensor:
     if weight.dim() != 2 or x.dim() < 1 or x.shape[-1] != weight.shape[1]:
         raise ValueError(f"{name}: x {tuple(x.shape)} does not match weight "
                          f"{tuple(weight.shape)}")
@@ -229,7 +269,7 @@ def _mx_linear(name: str, fn, x: torch.Tensor, weight: torch.Tensor) -> torch.Te
         raise ValueError(f"{name} needs tokens, in_features and out_features to be positive "
                          f"multiples of {_MX_TILE}, got T={T} in={weight.shape[1]} "
                          f"out={weight.shape[0]}")
-    return fn.apply(x, weight)
+    return fn.apply(x, weight, *extra)
 
 
 def linear_mxfp8(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
@@ -243,7 +283,8 @@ def linear_mxfp8(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
     return _mx_linear("linear_mxfp8", _LinearMxfp8Fn, x, weight)
 
 
-def linear_mxfp4(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
+def linear_mxfp4(x: torch.Tensor, weight: torch.Tensor, grad_rounding: str = "nearest",
+                 seed: int | None = None) -> torch.Tensor:
     """``x @ weight.T`` whose forward product, input gradient and weight gradient
     all run on the MXFP4 GEMM (``gemm_mxfp4_tn``), each operand quantised in
     blocks of 32 along the axis its product contracts.  ``x`` is ``[..., in]``,
@@ -252,10 +293,27 @@ def linear_mxfp4(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
     gradient keeps the ``main_grad`` contract of :class:`Linear`.  Raises
     ``ValueError`` unless :func:`is_mxfp4_linear_shape` holds.
 
-    All three products round to nearest even, like the rest of the MX code
-    here.  FP4 gradients under round-to-nearest-even are biased; the switch
-    changes the numerics of the step (e2m1's own error against the bf16
-    product is ~21 % per product), and no convergence run backs it yet."""
+    By default all three products round to nearest even, like the rest of the
+    MX code here.  FP4 gradients under round-to-nearest-even are biased: the
+    OCP scale clamps scaled block maxima in (6, 8) to 6, and with the
+    project's reference quantiser every input gradient comes out shrunk by
+    about 8 % (projection of the error of ``dx`` on the exact product of the
+    same operands).  ``grad_rounding="stochastic"`` quantises ``dy``, in both
+    of its images, with stochastic rounding and a block scale that does not
+    clip (``quantize_mxfp4*(.., "stochastic", seed)``): the error is zero in the
+    mean (that of the mean of N draws falls as 1/sqrt(N)).  One draw has the
+    error norm of round-to-nearest on evenly filled blocks and a larger one on
+    blocks whose elements lie mostly far below the block maximum, which
+    round-to-nearest sends to zero.  The forward product and the ``W^T`` / ``x^T``
+    images of the backward stay round-to-nearest.  The row image of ``dy``
+    draws with ``seed`` and its transposed image with ``seed + 1``, whether one
+    or both gradients are needed; ``seed=None`` takes ``sr_next()`` at forward
+    time.  Either way the switch changes the numerics of the step (e2m1's own
+    error against the bf16 product is ~21 % per product), and no convergence
+    run backs either rounding yet."""
+    _check_grad_rounding(grad_rounding, seed)
+    if grad_rounding == "stochastic":
+        return _mx_linear("linear_mxfp4", _LinearMxfp4SrFn, x, weight, seed)
     return _mx_linear("linear_mxfp4", _LinearMxfp4Fn, x, weight)
 
 
@@ -377,22 +435,32 @@ class Linear(nn.Linear):
     for it, i.e. tokens, in and out features are multiples of 256.  Any other
     call (toy shapes, a ragged batch) silently takes the bf16 path.
     ``compute="mxfp4"`` does the same with the MXFP4 GEMM
-    (:func:`linear_mxfp4`, :func:`is_mxfp4_linear_shape`)."""
+    (:func:`linear_mxfp4`, :func:`is_mxfp4_linear_shape`);
+    ``grad_rounding="stochastic"`` (MXFP4 only) quantises the output gradient
+    of those calls with stochastic rounding, a seed from ``mxfp4.sr_next()`` per
+    call."""
 
     COMPUTE = ("bf16", "mxfp8", "mxfp4")
     _MX_FN = {"mxfp8": _LinearMxfp8Fn, "mxfp4": _LinearMxfp4Fn}
 
-    def __init__(self, in_features: int, out_features: int, compute: str = "bf16", **kw):
+    def __init__(self, in_features: int, out_features: int, compute: str = "bf16",
+                 grad_rounding: str = "nearest", **kw):
         if compute not in self.COMPUTE:
             raise ValueError(f"compute must be one of {self.COMPUTE}, got {compute!r}")
+        _check_grad_rounding(grad_rounding)
+        if grad_rounding != "nearest" and compute != "mxfp4":
+            raise ValueError(f"grad_rounding={grad_rounding!r} needs compute=\"mxfp4\", got {compute!r}")
         super().__init__(in_features, out_features, bias=False, **kw)
         self.compute = compute
+        self.grad_rounding = grad_rounding
         self.weight._mxk_direct_grad = True
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         fn = self._MX_FN.get(self.compute)
         if fn is not None and is_mxfp8_linear_shape(      # one predicate for both formats
                 x.numel() // self.in_features, self.in_features, self.out_features):
+            if self.grad_rounding == "stochastic":
+                return _LinearMxfp4SrFn.apply(x, self.weight, None)
             return fn.apply(x, self.weight)
         return _LinearFn.apply(x, self.weight)
 

@@ -72,6 +72,31 @@ def resolve_linear_dtype(args) -> str:
     return v
 
 
+GRAD_ROUNDINGS = ("nearest", "stochastic")
+
+
+def resolve_grad_rounding(args) -> str:
+    """``--grad-rounding``, else the environment variable ``MXK_GRAD_ROUNDING``
+    (so ``bench.py --mode ddp`` can be A/B'd unchanged), else nearest.
+    ``stochastic`` needs the MXFP4 linear layers (``run_ddp_bench`` checks)."""
+    v = getattr(args, "grad_rounding", None) or os.environ.get("MXK_GRAD_ROUNDING") or "nearest"
+    if v not in GRAD_ROUNDINGS:
+        raise ValueError(f"grad rounding must be one of {', '.join(GRAD_ROUNDINGS)}, got {v!r}")
+    return v
+
+
+def resolve_sr_seed(args) -> int:
+    """``--sr-seed``, else the environment variable ``MXK_SR_SEED``, else 0: the
+    seed of the stochastic gradient rounding, in [0, 2^64)."""
+    v = getattr(args, "sr_seed", None)
+    if v is None:
+        v = os.environ.get("MXK_SR_SEED") or 0
+    v = int(v)
+    if not 0 <= v < 2 ** 64:
+        raise ValueError(f"sr seed must be in [0, 2^64), got {v}")
+    return v
+
+
 def resolve_doc_len(args) -> int:
     """``--doc-len``, else the environment variable ``MXK_DOC_LEN`` (so
     ``bench.py --mode ddp`` can be A/B'd unchanged), else 0: off.  A positive
@@ -187,6 +212,11 @@ def run_ddp_bench(args) -> dict:
         backend = "gloo"
     mxdist.init_distributed(backend=backend, device=dev if backend == "nccl" else None)
     linear_dtype = resolve_linear_dtype(args)
+    grad_rounding = resolve_grad_rounding(args)
+    sr_seed = resolve_sr_seed(args)
+    if grad_rounding != "nearest" and linear_dtype != "mxfp4":
+        raise ValueError(f"grad rounding {grad_rounding!r} needs the mxfp4 linear dtype, "
+                         f"got {linear_dtype!r}")
     cfg = LlamaConfig.llama3_8b()
     model_name = "Llama-3-8B"
     if getattr(args, "layers", None):
@@ -196,6 +226,7 @@ def run_ddp_bench(args) -> dict:
         cfg = LlamaConfig.tiny()
         model_name = "tiny-llama (test)"
     cfg.linear_dtype = linear_dtype
+    cfg.grad_rounding = grad_rounding
     seq, mb = args.seq_len, args.micro_batch
     bucket_mb = getattr(args, "bucket_mb", 512.0)
     # the TunableOp table only matters when a library GEMM runs in the step
@@ -228,7 +259,17 @@ def run_ddp_bench(args) -> dict:
     if getattr(args, "resume", None):
         from . import checkpoint
         start_step = checkpoint.load(args.resume, ddp, opt)
+
+    def reseed(steps_run):
+        # stochastic gradient rounding: the seed source restarts at every step
+        # from (seed, rank, global step), so a resumed run draws what the
+        # uninterrupted one drew
+        if grad_rounding == "stochastic":
+            from ..ops.mxfp4 import sr_reseed
+            sr_reseed(sr_seed, rank, start_step + steps_run)
+
     for i in range(args.warmup):
+        reseed(i)
         train_step(model, ddp, opt, batches[i % nbatches], docs[i % nbatches])
     sync()
     mxdist.barrier()
@@ -244,6 +285,7 @@ def run_ddp_bench(args) -> dict:
         # a training signal)
         for i in range(args.steps):
             b = (args.warmup + i) % nbatches
+            reseed(args.warmup + i)
             losses.append(train_step(model, ddp, opt, batches[b], docs[b]))
         sync()
     mxdist.barrier()
@@ -273,6 +315,7 @@ def run_ddp_bench(args) -> dict:
         "vs_baseline": None,
         "dtype": "bf16",
         "linear_dtype": cfg.linear_dtype,
+        "grad_rounding": cfg.grad_rounding,
         "data": "synthetic (uniform random token ids), random-init weights"
                 + (f", rows packed with documents of mean length {doc_len} (attention masked at "
                    f"their boundaries)" if doc_info else ""),
@@ -316,6 +359,13 @@ def main(argv=None) -> int:
     p.add_argument("--linear-dtype", choices=list(LINEAR_DTYPES), default=None,
                    help="products of wqkv / wo / w13 / w2: bf16 kernels (default), the MXFP8 or "
                         "the MXFP4 GEMM; unset, the environment variable MXK_LINEAR_DTYPE decides")
+    p.add_argument("--grad-rounding", choices=list(GRAD_ROUNDINGS), default=None,
+                   help="rounding of the output gradients' MXFP4 images (needs --linear-dtype mxfp4): "
+                        "nearest (default) or stochastic; unset, the environment variable "
+                        "MXK_GRAD_ROUNDING decides")
+    p.add_argument("--sr-seed", type=int, default=None, metavar="N",
+                   help="seed of the stochastic gradient rounding; unset, the environment "
+                        "variable MXK_SR_SEED decides (default 0)")
     p.add_argument("--doc-len", type=int, default=None, metavar="MEAN",
                    help="pack each synthetic row with documents of this mean length and mask "
                         "attention at their boundaries; unset, the environment variable "

@@ -16,19 +16,46 @@
 // moved into a function compiles to another instruction stream
 // (profiles/mx_gemm_core/), while every instantiation of a kernel template is
 // the code its hand-written copy was (profiles/mx_quantize/).
+//
+// Rounding is a policy of the format struct.  A stochastic format (E2m1Sr of
+// quantize_mxfp4_sr.hip) is launched with one more argument, a uint64_t seed,
+// which every kernel and launcher below takes as the pack Seed...:
+// empty for the nearest-rounding formats, whose kernels keep their parameter
+// lists and instruction streams (profiles/mxfp4_sr/isa_diff.txt), and for them
+// quantize_quarter discards the stochastic branch.  A stochastic format has
+//   block_exp(amax)       its own (non-clipping) block exponent,
+//   random(SrLane, r)     the 4 random words of elements 8 g .. 8 g + 7 of row i
+//                         of the OUTPUT image (8 x 16 bits, element j takes
+//                         r[j >> 1] >> 16 (j & 1)),
+//   convert(v, u16)       the element's code from the scaled value and its bits,
+// so an image depends on (seed, element) alone and the transposing kernel's
+// image is the row kernel's of the transposed copy.
 #pragma once
 #include "mx_gemm_core.h"
 
 namespace mxk {
 namespace mx {
 
+// The stochastic arguments of quantize_quarter for the lane that converts
+// elements 8 g .. 8 g + 7 of row i of the output image; both indices are below
+// 2^32 (the launchers' gate), so they are the two counter words.
+constexpr long kSrMaxIndex = 0xFFFFFFFFL;
+struct SrLane {
+  uint32_t g, i;
+  uint64_t seed;
+};
+__device__ __forceinline__ SrLane sr_lane(long g, long i, uint64_t seed) {
+  return SrLane{static_cast<uint32_t>(g), static_cast<uint32_t>(i), seed};
+}
+
 // 8 consecutive elements of an MX block (4 dwords of two bf16 each, memory
 // order) whose other 24 are in the lane's DPP quad: the 8 codes packed in
 // memory order; returns the block's exponent.  Every lane of the quad must be
 // active.
-template <class Fmt>
+// sr (stochastic formats only): the SrLane of these 8 elements.
+template <class Fmt, class... Sr>
 __device__ __forceinline__ int quantize_quarter(const uint32_t (&w)[4],
-                                                uint32_t (&out)[Fmt::kBits / 4]) {
+                                                uint32_t (&out)[Fmt::kBits / 4], Sr... sr) {
   float f[8];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -45,10 +72,19 @@ __device__ __forceinline__ int quantize_quarter(const uint32_t (&w)[4],
   const float inv = Fmt::inv_scale(e);
 #pragma unroll
   for (int i = 0; i < Fmt::kBits / 4; ++i) out[i] = 0;
+  if constexpr (sizeof...(Sr) != 0) {
+    uint32_t r[4];
+    Fmt::random(sr..., r);
 #pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const float v = fminf(fmaxf(f[i] * inv, -Fmt::kMax), Fmt::kMax);   // explicit saturation
-    out[i * Fmt::kBits / 32] |= Fmt::convert(v) << (i * Fmt::kBits % 32);
+    for (int i = 0; i < 8; ++i)   // |f[i] * inv| <= kMax: the exponent does not clip
+      out[i * Fmt::kBits / 32] |= Fmt::convert(f[i] * inv, (r[i >> 1] >> (16 * (i & 1))) & 0xFFFFu)
+                                  << (i * Fmt::kBits % 32);
+  } else {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const float v = fminf(fmaxf(f[i] * inv, -Fmt::kMax), Fmt::kMax);   // explicit saturation
+      out[i * Fmt::kBits / 32] |= Fmt::convert(v) << (i * Fmt::kBits % 32);
+    }
   }
   return e;
 }
@@ -65,10 +101,11 @@ __device__ __forceinline__ void store_quarter(uint8_t* qp, const uint32_t (&out)
 
 // ---- row quantiser ------------------------------------------------------------
 // One lane per 8 consecutive elements, 4 lanes (a DPP quad) per MX block.
-template <class Fmt, bool VEC>
+template <class Fmt, bool VEC, class... Seed>
 __global__ void __launch_bounds__(256)
 quantize_rows_kernel(const uint16_t* __restrict__ x, uint8_t* __restrict__ q,
-                     uint8_t* __restrict__ s, long R, int K, long ldx, long ldq, long lds) {
+                     uint8_t* __restrict__ s, long R, int K, long ldx, long ldq, long lds,
+                     Seed... seed) {
   const long per_row = K >> 3;
   const long gid = static_cast<long>(blockIdx.x) * blockDim.x + threadIdx.x;
   // K % 32 == 0, so a quad never straddles a row and leaves the grid whole
@@ -85,7 +122,7 @@ quantize_rows_kernel(const uint16_t* __restrict__ x, uint8_t* __restrict__ q,
     for (int i = 0; i < 4; ++i) w[i] = xp[2 * i] | (static_cast<uint32_t>(xp[2 * i + 1]) << 16);
   }
   uint32_t out[Fmt::kBits / 4];
-  const int e = quantize_quarter<Fmt>(w, out);
+  const int e = quantize_quarter<Fmt>(w, out, sr_lane(c8, row, seed)...);
   uint8_t* qp = q + row * ldq + c8 * Fmt::kBits;
   if constexpr (VEC) {
     store_quarter<Fmt>(qp, out);
@@ -100,21 +137,22 @@ quantize_rows_kernel(const uint16_t* __restrict__ x, uint8_t* __restrict__ q,
 // 32 == 0; q packed codes (row stride ldq bytes); s E8M0 bytes [R][K / 32].
 // The row kernel with 16-B loads and one packed store per lane, or going by
 // element.
-template <class Fmt>
+template <class Fmt, class... Seed>
 int launch_quantize_rows(const void* x, void* q, void* s, long R, int K, long ldx, long ldq, long lds,
-                         hipStream_t stream) {
+                         hipStream_t stream, Seed... seed) {
   if (!x || !q || !s || R <= 0 || K <= 0 || K % 32 || ldx < K || ldq < K * Fmt::kBits / 8 ||
       lds < K / 32)
     return static_cast<int>(hipErrorInvalidValue);
+  if (sizeof...(Seed) != 0 && R > kSrMaxIndex) return static_cast<int>(hipErrorInvalidValue);
   const long lanes = R * (K / 8);
   const long blocks = (lanes + 255) / 256;
   if (blocks > 0x7FFFFFFFL) return static_cast<int>(hipErrorInvalidValue);
   // 16-B loads of x, kBits-byte stores of q: everything else goes by element
   const bool vec = aligned(x, 16) && ldx % 8 == 0 && aligned(q, Fmt::kBits) && ldq % Fmt::kBits == 0;
-  const auto kernel = vec ? quantize_rows_kernel<Fmt, true> : quantize_rows_kernel<Fmt, false>;
+  const auto kernel = vec ? quantize_rows_kernel<Fmt, true, Seed...> : quantize_rows_kernel<Fmt, false, Seed...>;
   hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, stream,
                      static_cast<const uint16_t*>(x), static_cast<uint8_t*>(q),
-                     static_cast<uint8_t*>(s), R, K, ldx, ldq, lds);
+                     static_cast<uint8_t*>(s), R, K, ldx, ldq, lds, seed...);
   MXK_RETURN_LAUNCH_STATUS();
 }
 
@@ -166,6 +204,15 @@ int launch_quantize_rows(const void* x, void* q, void* s, long R, int K, long ld
 // against e4m3's 710 (271 against 47 of them v_cmp, the seven threshold
 // compares per element of mxfp4::f32_to_e2m1), and 4 waves x 954 issue cycles
 // x 32 tiles per CU are 51 us of the 59 at [16384, 4096].
+//
+// The stochastic e2m1 instantiation (quantize_mxfp4_sr.hip; profiles/mxfp4_sr/):
+// 1783 VALU instructions per lane and tile (dual: 3425 against 1769), 467 of
+// them v_cmp and 103 (against 36) the 32-bit multiplies that the four Philox
+// calls add (v_mul_lo / v_mul_hi_u32, v_mad_u64_u32); the wave-uniform key
+// schedule runs on the scalar unit (408 scalar instructions against 86);
+// measured 0.093 / 0.281 / 0.083 ms at
+// the three shapes, 1.50-1.53x the nearest form of the same run (dual 0.165 /
+// 0.522 / 0.147 ms, 1.61-1.68x), less than the static ratio of 1.87 (1.94).
 #ifndef MXK_MX_TR_ROWS
 #define MXK_MX_TR_ROWS 128   // 256 measured 6-8 % slower for e2m1 (above); e4m3 not measured
 #endif
@@ -175,11 +222,11 @@ constexpr int kTrLdsRow = kTrRows * 2 + 8;   // bytes
 constexpr int kTrLanesPerCol = kTrRows / 8;  // lanes that share a column in the store phase
 constexpr int kTrColsPerPass = 256 / kTrLanesPerCol;
 
-template <class Fmt, bool VEC, bool DUAL>
+template <class Fmt, bool VEC, bool DUAL, class... Seed>
 __global__ void __launch_bounds__(256)
 quantize_tr_kernel(const uint16_t* __restrict__ x, uint8_t* __restrict__ q, uint8_t* __restrict__ s,
                    uint8_t* __restrict__ qt, uint8_t* __restrict__ st, long R, long C, long ldx,
-                   long ldq, long lds, long ldqt, long ldst) {
+                   long ldq, long lds, long ldqt, long ldst, Seed... seed) {
   constexpr int kPack = Fmt::kBits == 4;   // element index >> kPack = byte of a row
   __shared__ __attribute__((aligned(8))) char tile[kTrCols * kTrLdsRow];
   const int t = threadIdx.x;
@@ -211,7 +258,7 @@ quantize_tr_kernel(const uint16_t* __restrict__ x, uint8_t* __restrict__ q, uint
       }
       if constexpr (DUAL) {
         uint32_t out[Fmt::kBits / 4];
-        const int e = quantize_quarter<Fmt>(w[h], out);
+        const int e = quantize_quarter<Fmt>(w[h], out, sr_lane(col >> 3, row, seed)...);
         if (row < R && col < C) {   // C % 32 == 0: whole blocks
           uint8_t* qp = q + row * ldq + (col >> kPack);
           if constexpr (VEC) {
@@ -243,7 +290,8 @@ quantize_tr_kernel(const uint16_t* __restrict__ x, uint8_t* __restrict__ q, uint
     const uint2 b = *reinterpret_cast<const uint2*>(tp + 8);
     const uint32_t w[4] = {a.x, a.y, b.x, b.y};
     uint32_t out[Fmt::kBits / 4];
-    const int e = quantize_quarter<Fmt>(w, out);
+    // stochastic: the transposed image of a dual call draws with seed + 1
+    const int e = quantize_quarter<Fmt>(w, out, sr_lane(row >> 3, c0 + cl, seed + (DUAL ? 1u : 0u))...);
     const long c = c0 + cl;
     if (row < R && c < C) {   // R % 32 == 0: whole blocks
       uint8_t* qp = qt + c * ldqt + (row >> kPack);
@@ -263,13 +311,16 @@ quantize_tr_kernel(const uint16_t* __restrict__ x, uint8_t* __restrict__ q, uint
 // ldqt bytes), st
 // E8M0 bytes [C][R / 32].  dual: also q / s, the image of launch_quantize_rows
 // (C % 32 == 0 as well).
-template <class Fmt>
+template <class Fmt, class... Seed>
 int launch_quantize_tr(bool dual, const void* x, void* q, void* s, void* qt, void* st, long R, long C,
-                       long ldx, long ldq, long lds, long ldqt, long ldst, hipStream_t stream) {
+                       long ldx, long ldq, long lds, long ldqt, long ldst, hipStream_t stream,
+                       Seed... seed) {
   constexpr int kB = Fmt::kBits;
   if (!x || !qt || !st || R <= 0 || C <= 0 || R % 32 || ldx < C || ldqt < R / (8 / kB) || ldst < R / 32)
     return static_cast<int>(hipErrorInvalidValue);
   if (dual && (!q || !s || C % 32 || ldq < C / (8 / kB) || lds < C / 32))
+    return static_cast<int>(hipErrorInvalidValue);
+  if (sizeof...(Seed) != 0 && (R > kSrMaxIndex || C > kSrMaxIndex))
     return static_cast<int>(hipErrorInvalidValue);
   const long gx = (R + kTrRows - 1) / kTrRows, gy = (C + kTrCols - 1) / kTrCols;
   if (gx > 0x7FFFFFFFL || gy > 65535) return static_cast<int>(hipErrorInvalidValue);
@@ -280,14 +331,14 @@ int launch_quantize_tr(bool dual, const void* x, void* q, void* s, void* qt, voi
   auto go = [&](auto kernel) {
     hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, static_cast<const uint16_t*>(x),
                        static_cast<uint8_t*>(q), static_cast<uint8_t*>(s), static_cast<uint8_t*>(qt),
-                       static_cast<uint8_t*>(st), R, C, ldx, ldq, lds, ldqt, ldst);
+                       static_cast<uint8_t*>(st), R, C, ldx, ldq, lds, ldqt, ldst, seed...);
   };
   if (dual) {
-    if (vec) go(quantize_tr_kernel<Fmt, true, true>);
-    else go(quantize_tr_kernel<Fmt, false, true>);
+    if (vec) go(quantize_tr_kernel<Fmt, true, true, Seed...>);
+    else go(quantize_tr_kernel<Fmt, false, true, Seed...>);
   } else {
-    if (vec) go(quantize_tr_kernel<Fmt, true, false>);
-    else go(quantize_tr_kernel<Fmt, false, false>);
+    if (vec) go(quantize_tr_kernel<Fmt, true, false, Seed...>);
+    else go(quantize_tr_kernel<Fmt, false, false, Seed...>);
   }
   MXK_RETURN_LAUNCH_STATUS();
 }
