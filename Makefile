@@ -40,7 +40,7 @@ KERNEL_SRCS := native/kernels/gemm_bf16.hip native/kernels/vector_add.hip \
 KERNEL_OBJS := $(patsubst native/kernels/%.hip,$(BUILD)/kernels/%.o,$(KERNEL_SRCS))
 EXP_SRCS    := $(KERNEL_SRCS) $(wildcard native/kernels/experiments/*.hip)
 EXP_OBJS    := $(patsubst native/kernels/%.hip,$(BUILD)/exp/%.o,$(EXP_SRCS))
-KERNEL_HDRS := $(wildcard native/kernels/*.h)
+KERNEL_HDRS := $(wildcard native/kernels/*.h native/kernels/experiments/*.h)
 
 NODE_SRCS := $(wildcard native/libmxnode/*.cc)
 NODE_OBJS := $(patsubst native/libmxnode/%.cc,$(BUILD)/node/%.o,$(NODE_SRCS))

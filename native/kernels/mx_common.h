@@ -770,6 +770,33 @@ struct SchedHB {
   }
 };
 
+// The layout kernel's own positions (gemm_x2_core.h x2_ktile, SCHED bit 0
+// clear; gemm_bf16.hip's w4i schedule).  "read" = one operand fragment (one
+// ds_read_b128 for a K-major operand, two ds_read_b64_tr_b16 for an N/M-major
+// one):
+//   m 1..15 odd   A k-half-1 fragments from X           m 19  barrier #1
+//   m 21..49 /4   B k-half-1 fragments from X
+//   m 23..51 /4   DMA of stage s+2, A pieces -> X.A     m 55  barrier #2
+//   m 57..99 /6   DMA of stage s+2, B pieces -> X.B
+//   m 96          vmcnt(15) + barrier #3 (stage s+1 in Y landed everywhere)
+//   m 97..127 odd next k-half-0 fragments from Y (B, then A)
+struct SchedX2 {
+  static constexpr int W1 = 19, B1 = 19, W2 = 55, B2 = 55, W3 = 96, VM3 = 15, B3 = 96;
+  __host__ __device__ static constexpr int a1(int m) { return m < 16 && (m & 1) ? m >> 1 : -1; }
+  __host__ __device__ static constexpr int b1(int m) {
+    return m >= 20 && m < 52 && (m & 3) == 1 ? (m - 21) >> 2 : -1;
+  }
+  __host__ __device__ static constexpr int adma(int m) {
+    return m >= 20 && m < 52 && (m & 3) == 3 ? (m - 23) >> 2 : -1;
+  }
+  __host__ __device__ static constexpr int bdma(int m) {
+    return m >= 57 && (m - 57) % 6 == 0 && (m - 57) / 6 < 8 ? (m - 57) / 6 : -1;
+  }
+  __host__ __device__ static constexpr int k0(int m) {
+    return m > 96 && (m & 1) ? (m - 97) >> 1 : -1;
+  }
+};
+
 // SCHED 3 ("HB-earlyB"): SchedHB with every B piece of stage s+2 issued
 // before the stage-(s+1) wait (59..80 every 3), so that wait covers only
 // pieces issued a full K-tile earlier: vmcnt(16).

@@ -29,6 +29,9 @@ done
 
 step() { echo "== $*"; }
 run() { if [ $PLAN -eq 1 ]; then echo "+ $*"; else "$@"; fi; }
+run_filter() {   # run with a pipe on stdin: the plan drains it, so the writer never meets a closed pipe
+  if [ $PLAN -eq 1 ]; then cat >/dev/null; echo "+ $*"; else "$@"; fi
+}
 record() {   # record <config> <json>
   if [ $PLAN -eq 1 ]; then echo "+ record config $1"; return; fi
   python3 -c 'import json,sys; d=json.loads(sys.argv[2]); d["config"]=int(sys.argv[1]); print(json.dumps(d))' \
@@ -74,7 +77,7 @@ run kubectl apply -f "$REPO/deploy/examples/hip-vector-add.yaml"
 wait_pod hip-vector-add 300s
 # every RESULT line passes AND the pod sees exactly its 1 allocated gfx950
 # GPU / render node (BASELINE.md:37)
-results_of hip-vector-add | run env PYTHONPATH="$REPO" python3 -m mxk8s.validate.isolation --gpus 1 --arch gfx950
+results_of hip-vector-add | run_filter env PYTHONPATH="$REPO" python3 -m mxk8s.validate.isolation --gpus 1 --arch gfx950
 record 2 '{"test":"hip-vector-add","pass":true,"isolation":true}'
 
 step "config 3: validator pod amd.com/gpu=1, bf16 MFMA GEMM"

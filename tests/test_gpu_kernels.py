@@ -295,16 +295,12 @@ def test_add_rmsnorm_fwd_bwd(cuda_device, rows, H):
     assert (w.grad.float() - wr.grad).abs().max() <= 2e-2 * wr.grad.abs().max() + 1e-2
 
 
-@pytest.mark.parametrize("variant", [0, 1, 2, 3])
-@pytest.mark.parametrize("layout", ["tn", "nn", "nt_wgrad", "tt"])
-@pytest.mark.parametrize("M,N,K", [(512, 768, 320), (4096, 4096, 192)])
-def test_gemm_layouts_vs_fp32(cuda_device, layout, variant, M, N, K):
-    """Layout-generic MFMA GEMM (K-major / N-major operands, tr_b16 reads);
-    every schedule (auto, x, x2, x2 at hipBLASLt positions); 4096^2 puts the XCD
-    super-block tile map in play."""
+def _check_gemm_layout(device, layout, variant, M, N, K):
+    """gemm_bf16_ex of one operand layout into a NaN-filled output, the whole
+    output against fp32; returns the operands for further calls."""
     from mxk8s.ops.gemm import gemm_bf16_ex
-    g = torch.Generator(device=cuda_device).manual_seed(11)
-    r = lambda *s: (torch.rand(*s, device=cuda_device, generator=g) * 2 - 1).bfloat16()  # noqa: E731
+    g = torch.Generator(device=device).manual_seed(11)
+    r = lambda *s: (torch.rand(*s, device=device, generator=g) * 2 - 1).bfloat16()  # noqa: E731
     if layout == "tn":
         a, b, ak, bk = r(M, K), r(N, K), True, True
         ref = a.float() @ b.float().t()
@@ -317,12 +313,34 @@ def test_gemm_layouts_vs_fp32(cuda_device, layout, variant, M, N, K):
     else:
         a, b, ak, bk = r(K, M), r(K, N), False, False
         ref = a.float().t() @ b.float()
-    out = torch.full((M, N), float("nan"), device=cuda_device, dtype=torch.bfloat16)
+    out = torch.full((M, N), float("nan"), device=device, dtype=torch.bfloat16)
     assert gemm_bf16_ex(a, b, ak, bk, out, variant=variant)
     err = (out.float() - ref).abs().max().item()
     assert err <= 2 ** -7 * ref.abs().max().item() + 1e-3, err
+    return a, b, ak, bk, out
+
+
+@pytest.mark.parametrize("variant", [0, 1, 2, 3])
+@pytest.mark.parametrize("layout", ["tn", "nn", "nt_wgrad", "tt"])
+@pytest.mark.parametrize("M,N,K", [(512, 768, 320), (4096, 4096, 192)])
+def test_gemm_layouts_vs_fp32(cuda_device, layout, variant, M, N, K):
+    """Layout-generic MFMA GEMM (K-major / N-major operands, tr_b16 reads);
+    every schedule (auto, x, x2, x2 at hipBLASLt positions); 4096^2 puts the XCD
+    super-block tile map in play."""
+    from mxk8s.ops.gemm import gemm_bf16_ex
+    a, b, ak, bk, out = _check_gemm_layout(cuda_device, layout, variant, M, N, K)
     # shapes that do not tile fall back (nothing launched)
     assert not gemm_bf16_ex(a[:, :-64] if ak else a[:-64], b, ak, bk, out, variant=variant)
+
+
+@pytest.mark.parametrize("variant", [0, 1, 2, 3])
+@pytest.mark.parametrize("layout", ["tn", "nn", "nt_wgrad", "tt"])
+@pytest.mark.parametrize("K", [64, 128, 256])
+def test_gemm_layouts_short_k_vs_fp32(cuda_device, layout, variant, K):
+    """The shortest K loops of the layout kernels, two tiles each: one K-tile
+    (the single-stage prologue and the last-tile instance only), two (the
+    DMA-free pair) and four (one steady pair, then the tails)."""
+    _check_gemm_layout(cuda_device, layout, variant, 256, 512, K)
 
 
 @pytest.mark.parametrize("layout", ["tn", "nn", "nt_wgrad", "tt"])

@@ -188,6 +188,14 @@ def test_asm_dma_reads_no_fresh_valu_sgpr(src, tmp_path):
     assert valu_sgpr_to_vmem(asm) == {}
 
 
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
+def test_layout_gemm_records_asm_dma_reads_no_fresh_valu_sgpr(tmp_path):
+    """The same for the layout kernel's A/B records (experiments/gemm_layouts_exp.h)."""
+    asm = _asm("gemm_bf16_layouts.hip", str(tmp_path / "exp.s"), ("-DMXK_GEMM_EXPERIMENTS",))
+    assert "x2t_kernel" in asm
+    assert valu_sgpr_to_vmem(asm) == {}
+
+
 def asm_load_dests_touched(asm: str, kernel_re: str, wait: str) -> list[str]:
     """Instructions that read or write the destination registers of the
     inline-asm ``global_load`` run of a kernel's prologue before ``wait``
@@ -424,7 +432,8 @@ def test_attention_bwd256_asm_mfma_hazards_and_spills(src, tmp_path):
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
 @pytest.mark.parametrize("src,flags", [("gemm_bf16.hip", ()), ("gemm_bf16_layouts.hip", ()),
-                                       ("experiments/gemm_tn_exp.hip", ("-DMXK_GEMM_EXPERIMENTS",))])
+                                       ("experiments/gemm_tn_exp.hip", ("-DMXK_GEMM_EXPERIMENTS",)),
+                                       ("gemm_bf16_layouts.hip", ("-DMXK_GEMM_EXPERIMENTS",))])
 def test_no_accumulator_read_right_after_asm_mfma(src, flags, tmp_path):
     asm = _asm(src, str(tmp_path / (src.replace("/", "_") + ".s")), flags)
     assert "v_mfma" in asm
