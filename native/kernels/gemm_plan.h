@@ -187,6 +187,13 @@ inline GemmTnPlan gemm_tn_plan(const GemmOperands& o, int default_variant) {
 // staggered by XCD group (STAG) where it fits.  A production build runs
 // EPI 4 for 5 / 6 / 8, as for any other non-zero mode.  gu or dgu not 16-B
 // aligned, or K < 2 K-tiles, gives EPI 2 whatever the mode.
+// The g / u prefetch (EPI 4, EPI 6 and STAG) addresses gu through one buffer
+// resource based at gu's first row, with a 32-bit byte offset over the whole
+// [M][2F] matrix: past 4 GiB the offset wraps and pass 0 would read g / u of
+// rows 2^32 / (4F) further up.  So a gu of more than GEMM_BUF_RANGE - 16 bytes
+// (the resource's num_records, 0xFFFFFFF0) runs EPI 3 unstaggered wherever a
+// prefetching plan would have been taken: the same arithmetic through 64-bit
+// pointers (EPI 2 / 3 / 5 never prefetch and are left alone).
 // A route that surprises, kept as it is: in the experiments build the B-outer
 // order (MXK_X2_ORDER=1) exists for EPI 4 only and wins over the mode, so mode
 // 3 (and any other but 0 / 5 / 6) with order 1 runs EPI 4 B-outer, not EPI 3.
@@ -210,7 +217,13 @@ inline GemmDgradSwigluPlan gemm_dgrad_swiglu_plan(const GemmOperands& o, unsigne
   p.grid = nwg;
   const bool wide = mode != 0 && gu_bits % 16 == 0 && o.c_bits % 16 == 0 && o.K >= 2 * GEMM_BK;
   if (!wide) return p;
+  // bytes of gu [M][2F]: the prefetch's resource covers GEMM_BUF_RANGE - 16
+  const bool gu_fits = static_cast<long>(o.M) * o.ldc * 2 <= GEMM_BUF_RANGE - 16;
   p.epi = 4;
+  if (!gu_fits) {
+    p.epi = experiments_built && mode == 5 ? 5 : 3;   // 5 does not prefetch
+    return p;
+  }
   if (experiments_built) {
     const int cx = cus / 8;
     if (mode == 8 && nwg % 8 == 0 && cx > 0 && nwg / 8 >= 2 * cx && o.K % (2 * GEMM_BK) == 0 &&

@@ -43,6 +43,10 @@ void check_dgrad(const GemmOperands& o, unsigned gu_bits, int mode, int order, b
     if (p.stag ? !(ws_ok && p.epi == 4 && p.cx > 0 && p.grid == nwg + 8 * p.cx) : p.grid != nwg) ++bad;
     if (p.order && p.epi != 4) ++bad;
     if (p.epi != 2 && (gu_bits % 16 || o.c_bits % 16 || o.K < 2 * GEMM_BK)) ++bad;
+    // no g / u prefetch (EPI 4 / 6, STAG) over a gu the 32-bit offset cannot span
+    if (static_cast<long>(o.M) * o.ldc * 2 > GEMM_BUF_RANGE - 16 &&
+        (p.epi == 4 || p.epi == 6 || p.stag || p.order))
+      ++bad;
   }
 }
 }  // namespace
@@ -68,6 +72,22 @@ int main() {
                       check_dgrad({M, N, K, K, N, gemm_twice(N), 1, 0, 0, 0, 0}, narrow ? 8 : 0, mode,
                                   exp, exp, cus);
                 }
+  // dgrad-SwiGLU with gu on both sides of 4 GiB (M * 2F * 2 bytes): every mode, and exactly
+  // which side takes the prefetching default
+  for (int F : {256, 1024, 8192})
+    for (int dm : {-512, -256, 0, 256})
+      for (int K : {64, 128, 1024})
+        for (int exp = 0; exp < 2; ++exp)
+          for (int cus : {256, 240, 4}) {
+            const int M = static_cast<int>(GEMM_BUF_RANGE / (4L * F)) + dm;
+            const GemmOperands o{M, F, K, K, F, gemm_twice(F), 1, 0, 0, 0, 0};
+            for (int mode : {0, 3, 4, 5, 6, 8, -1})
+              for (int narrow = 0; narrow < 2; ++narrow)
+                check_dgrad(o, narrow ? 8 : 0, mode, exp, exp, cus);
+            const GemmDgradSwigluPlan p = gemm_dgrad_swiglu_plan(o, 0, 4, 0, exp, cus, true);
+            ++n;
+            if (p.status || p.epi != (K < 2 * GEMM_BK ? 2 : dm < 0 ? 4 : 3)) ++bad;
+          }
   // hostile integers: every field from {<= 0, odd, INT_MAX and near it}
   const int H[] = {INT_MIN, -256, -1, 0, 1, 64, 256, 1 << 24, INT_MAX - 255, INT_MAX - 63, INT_MAX};
   for (int M : H)

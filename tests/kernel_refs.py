@@ -7,8 +7,14 @@ sum of the absolute values of the terms the closed form adds, which is what an
 elementwise error bound has to be relative to (``mag == |ref|`` where nothing
 cancels).  ``tests/test_kernel_refs_cpu.py`` checks each form against
 ``torch.autograd`` / ``torch.optim.AdamW`` in float64.
+
+The two bf16 GEMMs with a SwiGLU epilogue have their own section: closed forms
+computed on the CPU with a bound per element instead of ``mag``, the inputs the
+CPU and GPU tests share, and a float32 emulation of each epilogue.
 """
 from __future__ import annotations
+
+import math
 
 import torch
 
@@ -74,6 +80,215 @@ def swiglu_bwd(g, u, dh):
     mag_dg = t.abs() * (1 + g.abs() * one_minus_s)
     du = dh * g * s
     return dg, mag_dg, du, du.abs()
+
+
+# ------------------------------------------- SwiGLU-epilogue bf16 GEMMs ---
+# mxk_gemm_bf16_dgrad_swiglu and mxk_gemm_bf16_w13_swiglu: fp64 on the CPU
+# (no GPU BLAS), each result with its per-element error bound.
+# tests/test_gpu_swiglu_gemm_numerics.py derives the bounds.
+GEMM_ATOL = 1e-30
+_LOG2E_F32 = f32(-1.44269504)
+
+
+def gemm_term(a, b):
+    """a [M][K], b [K][N], bf16 values -> (d, S, delta) in fp64 on the CPU:
+    d = a b, S = |a| |b|, delta = K 2^-23 S (fp32 accumulation of exact
+    products, any order, with a factor 2 of margin)."""
+    a, b = a.detach().double().cpu(), b.detach().double().cpu()
+    S = a.abs() @ b.abs()
+    return a @ b, S, a.shape[1] * 2.0 ** -23 * S
+
+
+def _c(g):
+    """Relative error of the fp32 sigmoid chain at g: g * -log2(e) (2^-24
+    relative, |g| 2^-24 after exp2), one ulp each of exp2 and rcp, and a
+    handful of fp32 multiplies."""
+    return (g.abs() + 8) * 2.0 ** -23
+
+
+def dgrad_swiglu(dy, w2, gu):
+    """dy [M][K], w2 [K][F], gu [M][2F] = [g | u] -> (dg, bound_dg, du,
+    bound_du) with d = dy w2, s = sigmoid(g), f = 1 + g sigmoid(-g):
+    dg = d u s f,  du = d g s."""
+    d, _, delta = gemm_term(dy, w2)
+    g, u = gu.detach().double().cpu().chunk(2, -1)
+    s, f = torch.sigmoid(g), 1 + g * torch.sigmoid(-g)
+    c = _c(g)
+    dg = d * u * s * f
+    du = d * g * s
+    # the kernel evaluates f as (g + 1) - g s: its terms are |1 + g| and |g| s
+    bound_dg = (2.0 ** -8 * dg.abs() + delta * (u * s * f).abs() +
+                c * (d * u * s).abs() * ((1 + g).abs() + g.abs() * s) + GEMM_ATOL)
+    bound_du = 2.0 ** -8 * du.abs() + delta * (g * s).abs() + c * du.abs() + GEMM_ATOL
+    return dg, bound_dg, du, bound_du
+
+
+def w13_swiglu(x, w13):
+    """x [M][K], w13 [2F][K] = [gate | up] rows -> (gu, bound_gu, h, bound_h)
+    with gu = x w13^T and h = silu(g) u from the unrounded g, u."""
+    gu, _, delta = gemm_term(x, w13.detach().t())
+    g, u = gu.chunk(2, -1)
+    delta_g, delta_u = delta.chunk(2, -1)
+    s = torch.sigmoid(g)
+    dsilu = s * (1 + g * torch.sigmoid(-g))
+    h = g * s * u
+    bound_gu = 2.0 ** -8 * gu.abs() + delta + GEMM_ATOL
+    bound_h = (2.0 ** -8 * h.abs() + delta_g * (u * dsilu).abs() + delta_u * (g * s).abs() +
+               _c(g) * h.abs() + GEMM_ATOL)
+    return gu, bound_gu, h, bound_h
+
+
+def bound_ratio(got, ref, bound) -> float:
+    """max over elements of |got - ref| / bound; NaN / inf in ``got`` give inf."""
+    got = got.detach().double().cpu()
+    if not torch.isfinite(got).all():
+        return float("inf")
+    return ((got - ref).abs() / bound).max().item()
+
+
+def loose_fraction(ref, bound) -> float:
+    """Share of the elements whose bound exceeds 1.05 * 2^-8 |ref| + atol: on
+    the tight family at most 10 % may (the bound is then bf16 rounding and
+    little else, from the reference alone)."""
+    return (bound > 1.05 * 2.0 ** -8 * ref.abs() + GEMM_ATOL).double().mean().item()
+
+
+# Inputs of the two GEMMs, made on the CPU from a seed (the CPU emulation and
+# the GPU tests see the same tensors).  family "tight": every dot product adds
+# terms of one sign (S = |d|); "signed": plain signed operands, d cancels.
+# Magnitudes lie in [2^-4, 1.5): no product of two operands is below 2^-60.
+DGRAD_G_COLUMNS = (0.0, 2.0 ** -20, -1.2785, 17.0, -17.0, -30.0, -87.0, -88.5, -100.0, -126.0, 100.0,
+                   128.0)
+DGRAD_ZERO_ROW, DGRAD_ZERO_COL = 5, 3          # of dy / of W2
+DGRAD_U_ZERO_ROW, DGRAD_U_ZERO_COL = 9, 11
+
+
+def _operand(shape, gen, signed):
+    mag = 2.0 ** -4 + 1.4375 * torch.rand(shape, generator=gen, dtype=torch.float64)
+    if not signed:
+        return mag
+    return mag * torch.where(torch.rand(shape, generator=gen) < 0.5, -1.0, 1.0)
+
+
+def _signs(n, gen):
+    return torch.where(torch.rand(n, generator=gen) < 0.5, -1.0, 1.0).double()
+
+
+def _pow2(idx, mod, shift):
+    return torch.exp2(((idx % mod) - shift).double())
+
+
+def dgrad_g_column(i: int) -> int:
+    """Column of g that holds DGRAD_G_COLUMNS[i] in every row."""
+    return 7 + 19 * i
+
+
+def dgrad_inputs(M: int, F: int, K: int, family: str, seed: int = 0, row0: int = 0):
+    """-> bf16 (dy [M][K], w2 [K][F], gu [M][2F]).  dy row r scaled
+    2^((r mod 9) - 4), W2 column c scaled 2^((c mod 7) - 3) with a sign per
+    column, one zero row of dy and one zero column of W2; g random times
+    2^((r mod 5) - 2) with whole columns at DGRAD_G_COLUMNS, u with a
+    per-column scale, a zero row and a zero column.  row0 shifts the row
+    patterns (two row blocks of one matrix then differ)."""
+    assert family in ("tight", "signed") and F >= dgrad_g_column(len(DGRAD_G_COLUMNS) - 1) + 1
+    gen = torch.Generator().manual_seed(1000 * seed + row0 + (1 if family == "signed" else 0))
+    signed = family == "signed"
+    r, c = torch.arange(M) + row0, torch.arange(F)
+    dy = _operand((M, K), gen, signed) * _pow2(r, 9, 4)[:, None]
+    w2 = _operand((K, F), gen, signed) * (_pow2(c, 7, 3) * _signs(F, gen))[None, :] * 2.0 ** -4
+    dy[DGRAD_ZERO_ROW] = 0
+    w2[:, DGRAD_ZERO_COL] = 0
+    g = torch.randn((M, F), generator=gen, dtype=torch.float64) * _pow2(r, 5, 2)[:, None]
+    for i, v in enumerate(DGRAD_G_COLUMNS):
+        g[:, dgrad_g_column(i)] = v
+    u = _operand((M, F), gen, True) * _pow2(c, 3, 1)[None, :] * _pow2(r, 4, 1)[:, None]
+    u[DGRAD_U_ZERO_ROW] = 0
+    u[:, DGRAD_U_ZERO_COL] = 0
+    return dy.bfloat16(), w2.bfloat16(), torch.cat([g, u], -1).bfloat16()
+
+
+W13_ZERO_X_ROW, W13_ZERO_W_ROW = 6, 10
+
+
+def w13_inputs(M: int, F: int, K: int, family: str, seed: int = 0):
+    """-> bf16 (x [M][K], w13 [2F][K]).  x row r scaled 2^((r mod 5) - 4),
+    W13 row n scaled 2^((n mod 3) - 2) with a sign per output feature, one
+    zero row each; x then scaled by the power of two that puts max |gu| in
+    (32, 64], so the c(g) term stays small against bf16 rounding.  Seven of
+    eight negative gate features are scaled 2^-4 more: for g << 0 the weight
+    of delta_g in bound_h, |silu'(g) / silu(g)| |g| = |f| ~ |g|, would exceed
+    bf16 rounding, so most negative g stay above -4 and every eighth feature
+    still saturates the sigmoid."""
+    assert family in ("tight", "signed")
+    gen = torch.Generator().manual_seed(1000 * seed + 500 + (1 if family == "signed" else 0))
+    signed = family == "signed"
+    x = _operand((M, K), gen, signed) * _pow2(torch.arange(M), 5, 4)[:, None]
+    n = torch.arange(2 * F)
+    sign = _signs(2 * F, gen)
+    damp = torch.where((n < F) & (sign < 0) & (n % 8 != 1), 2.0 ** -4, 1.0)
+    w = _operand((2 * F, K), gen, signed) * (_pow2(n, 3, 2) * sign * damp)[:, None]
+    x[W13_ZERO_X_ROW] = 0
+    w[W13_ZERO_W_ROW] = 0
+    x, w = x.bfloat16().double(), w.bfloat16().double()
+    top = (x @ w.t()).abs().max().item()
+    x = x * 2.0 ** (5 - math.floor(math.log2(top)))
+    return x.bfloat16(), w.bfloat16()
+
+
+def dgrad_swiglu_emulated(dy, w2, gu, mutation: str = ""):
+    """The kernel's arithmetic in float32 on the CPU: fp32 accumulation, then
+    x = g * -log2(e), s = 1 / (1 + exp2(x)), t = d s, du = t g,
+    dg = (t u) ((g + 1) - g s), rounded to bf16.  ``mutation`` plants one
+    defect (tests/test_kernel_refs_cpu.py lists them)."""
+    M, K = dy.shape
+    F = w2.shape[1]
+    a, b = dy.float(), w2.float()
+    if mutation == "drop_last_ktile":
+        a, b = a[:, :K - 64], b[:K - 64]
+    d = a @ b if a.shape[1] else torch.zeros((M, F))
+    g, u = _swiglu_operands(gu.float(), F, mutation)
+    one, l2e = torch.tensor(1.0), torch.tensor(_LOG2E_F32, dtype=torch.float32)
+    x = g * l2e
+    s = one / (one + torch.exp2(-x if mutation == "sigmoid_neg" else x))
+    t = d * s
+    du = t * g
+    fac = one + g * s if mutation == "f_plus" else (g + one) - g * s
+    dg = (t * u) * fac
+    return dg.bfloat16(), du.bfloat16()
+
+
+def w13_swiglu_emulated(x, w13, mutation: str = ""):
+    """As above for the up-projection: gu = bf16(acc), h = bf16((g s) u) from
+    the fp32 accumulators."""
+    M, K = x.shape
+    F = w13.shape[0] // 2
+    a, b = x.float(), w13.float().t()
+    if mutation == "drop_last_ktile":
+        a, b = a[:, :K - 64], b[:K - 64]
+    acc = a @ b if a.shape[1] else torch.zeros((M, 2 * F))
+    g, u = _swiglu_operands(acc, F, mutation)
+    one, l2e = torch.tensor(1.0), torch.tensor(_LOG2E_F32, dtype=torch.float32)
+    x2 = g * l2e
+    s = one / (one + torch.exp2(-x2 if mutation == "sigmoid_neg" else x2))
+    return acc.bfloat16(), ((g * s) * u).bfloat16()
+
+
+def _swiglu_operands(gu, F, mutation):
+    """(g, u) as the epilogue pairs them with d, under a planted defect."""
+    M = gu.shape[0]
+    g, u = gu[:, :F].clone(), gu[:, F:].clone()
+    rows = torch.arange(M) % 128
+    if mutation == "rows_up_4":          # pass 0 (rows 0-31 of a 128-row block) reads 4 rows up
+        sel = rows < 32
+        g[sel], u[sel] = torch.roll(g, 4, 0)[sel], torch.roll(u, 4, 0)[sel]
+    elif mutation == "u_offset":         # u read at column offset F - 128
+        u = torch.roll(gu, 128, 1)[:, F:].clone()
+    elif mutation == "swap_64_127":      # gate and up exchanged for rows 64-127
+        sel = rows >= 64
+        g[sel], u[sel] = gu[:, F:][sel], gu[:, :F][sel]
+    else:
+        assert mutation in ("", "drop_last_ktile", "sigmoid_neg", "f_plus"), mutation
+    return g, u
 
 
 # ------------------------------------------------------------------- RoPE ---

@@ -356,6 +356,23 @@ def test_dgrad_swiglu_plan():
     assert dgrad_plan(8, exp=1, ws_ok=0, **big)[1] == dict(epi=4, order=0, stag=0, grid=512, cx=0)
     assert dgrad_plan(8, exp=1, **{**big, "K": 320})[1]["stag"] == 0       # K halves not whole K-tiles
     assert dgrad_plan(8, exp=1, **{**big, "M": 4096 - 256})[1]["stag"] == 0   # 480 tiles: < 2 rounds
+    # a gu of more than 2^32 - 16 bytes: the g / u prefetch (EPI 4 / 6, STAG) would wrap its
+    # 32-bit offset, so those plans run EPI 3 unstaggered; the 8-B form and EPI 5 stay
+    over = dict(M=1 << 20)                                      # M * 2F * 2 = 2^32 with F = 1024
+    huge = lambda epi: (0, dict(epi=epi, order=0, stag=0, grid=4096 * 4, cx=0))  # noqa: E731
+    for exp in (0, 1):
+        for mode in (3, 4, 6, 7, 8):
+            for order in (0, 1):
+                assert dgrad_plan(mode, exp=exp, order=order, **over) == huge(3), (mode, exp, order)
+        assert dgrad_plan(0, exp=exp, **over) == huge(2)
+        assert dgrad_plan(4, K=64, exp=exp, **over) == huge(2)
+        assert dgrad_plan(4, bits=(0, 0, 8, 0), exp=exp, **over) == huge(2)
+        assert dgrad_plan(5, exp=exp, **over) == huge(5 if exp else 3)
+        under = dgrad_plan(4, M=(1 << 20) - 256, exp=exp)       # 256 KiB short of 4 GiB: as ever
+        assert under == (0, dict(epi=4, order=0, stag=0, grid=4095 * 4, cx=0))
+    assert dgrad_plan(8, exp=1, M=(1 << 20) - 512)[1]["stag"] == 1
+    assert dgrad_plan(4, M=(1 << 22) + 256, F=256, K=128)[1]["epi"] == 3
+    assert dgrad_plan(4, M=(1 << 22) - 256, F=256, K=128)[1]["epi"] == 4
     # the gate
     for kw in (dict(M=0), dict(F=0), dict(K=0), dict(M=500), dict(F=1000), dict(K=200), dict(ld_dy=260),
                dict(ld_w2=1028), dict(ld_dy=248), dict(ld_w2=1016), dict(bits=(8, 0, 0, 0)),

@@ -3,7 +3,19 @@
 kernels with these forms, so a wrong form must not be able to hide a wrong
 kernel.  Tolerance 1e-12 relative to ``mag`` (fp64 round-off is 1.1e-16 per
 operation; the forms are a handful of operations and sums of at most 64
-terms)."""
+terms).
+
+The two SwiGLU-epilogue GEMMs (``dgrad_swiglu``, ``w13_swiglu``) come with a
+bound per element instead of ``mag``.  Their forms are checked against
+autograd as the others; their bounds are checked here against a float32
+emulation of each epilogue written as the kernel writes it (``exp2``, a
+reciprocal, the same association, bf16 rounding): the emulation must stay
+inside the bounds on both input families, every planted defect must leave them
+on the tight family, and on the tight family the bound must be bf16 rounding
+and little else (``loose_fraction`` <= 10 %, from the reference alone).
+``tests/test_gpu_swiglu_gemm_numerics.py`` derives the bounds."""
+import functools
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -140,6 +152,117 @@ def test_adamw_form_vs_torch_optim(step, wd, scale):
     _close(m1, st["exp_avg"], mag_m, "exp_avg")
     _close(v1, st["exp_avg_sq"], mag_v, "exp_avg_sq")
     _close(p1, par.detach(), mag_p, "param")
+
+
+# ---- the SwiGLU-epilogue GEMMs ------------------------------------------------
+def test_swiglu_gemm_forms_vs_autograd():
+    M, Fd, K = 6, 10, 12
+    dy, w2, gu = _r((M, K), 21), _r((K, Fd), 22), _r((M, 2 * Fd), 23) * 3
+    gu[0, :4] = torch.tensor([0.0, -1.2785, 40.0, -40.0], dtype=torch.float64)
+    ga = gu.clone().requires_grad_()
+    ((F.silu(ga[:, :Fd]) * ga[:, Fd:]) @ w2.t()).backward(dy)
+    dg, bound_dg, du, bound_du = R.dgrad_swiglu(dy, w2, gu)
+    g, u = gu[:, :Fd], gu[:, Fd:]
+    t = (dy @ w2) * u * torch.sigmoid(g)
+    _close(torch.cat([dg, du], -1), ga.grad, torch.cat([t.abs() * (1 + g.abs()), du.abs()], -1), "dgu")
+    assert (bound_dg >= 2.0 ** -8 * dg.abs()).all() and (bound_du >= 2.0 ** -8 * du.abs()).all()
+    x, w13 = _r((M, K), 24), _r((2 * Fd, K), 25)
+    gu2, bound_gu, h, bound_h = R.w13_swiglu(x, w13)
+    acc = x @ w13.t()
+    g = acc[:, :Fd]
+    _close(gu2, acc, x.abs() @ w13.t().abs(), "gu")
+    _close(h, F.silu(g) * acc[:, Fd:], h.abs(), "h")
+    assert (bound_gu >= 2.0 ** -8 * gu2.abs()).all() and (bound_h >= 2.0 ** -8 * h.abs()).all()
+    # the derivative that bound_h weighs delta_g with is silu'
+    ga = g.clone().requires_grad_()
+    (gs,) = torch.autograd.grad(F.silu(ga).sum(), ga)
+    _close(torch.sigmoid(g) * (1 + g * torch.sigmoid(-g)), gs, 1 + g.abs(), "silu'")
+
+
+DGRAD_CPU_SHAPES = [(256, 256, 64), (512, 512, 320), (256, 256, 1024)]
+W13_CPU_SHAPES = [(256, 128, 64), (512, 384, 320), (256, 128, 448)]
+DGRAD_MUTATIONS = ["rows_up_4", "u_offset", "swap_64_127", "drop_last_ktile", "sigmoid_neg", "f_plus"]
+W13_MUTATIONS = ["u_offset", "swap_64_127", "drop_last_ktile", "sigmoid_neg"]
+
+
+@functools.lru_cache(maxsize=None)
+def _dgrad_case(M, Fd, K, family):
+    inputs = R.dgrad_inputs(M, Fd, K, family)
+    return inputs, R.dgrad_swiglu(*inputs)
+
+
+@functools.lru_cache(maxsize=None)
+def _w13_case(M, Fd, K, family):
+    inputs = R.w13_inputs(M, Fd, K, family)
+    return inputs, R.w13_swiglu(*inputs)
+
+
+def test_swiglu_gemm_inputs_are_structured():
+    (dy, w2, gu), (dg, _, du, _) = _dgrad_case(256, 256, 64, "tight")
+    Fd = 256
+    assert (dy >= 0).all() and not dy[R.DGRAD_ZERO_ROW].any() and not w2[:, R.DGRAD_ZERO_COL].any()
+    assert ((w2 >= 0).all(0) | (w2 <= 0).all(0)).all() and (w2 < 0).any() and (w2 > 0).any()
+    for i, v in enumerate(R.DGRAD_G_COLUMNS):
+        assert (gu[:, R.dgrad_g_column(i)] == torch.tensor(v).bfloat16()).all()
+    assert not gu[R.DGRAD_U_ZERO_ROW, Fd:].any() and not gu[:, Fd + R.DGRAD_U_ZERO_COL].any()
+    assert gu[:, :Fd].abs().max() <= 250
+    for family in ("tight", "signed"):
+        (x, w13), (gu_ref, _, _, _) = _w13_case(256, 128, 448, family)
+        assert 32 < gu_ref.abs().max() <= 64
+        assert not x[R.W13_ZERO_X_ROW].any() and not w13[R.W13_ZERO_W_ROW].any()
+    (x, w13), _ = _w13_case(256, 128, 448, "tight")
+    assert (x >= 0).all() and ((w13 >= 0).all(1) | (w13 <= 0).all(1)).all()
+    # no operand product near the flush-to-zero range
+    for a, b in ((dy, w2), (x, w13)):
+        assert a[a != 0].abs().min().double() * b[b != 0].abs().min().double() > 2.0 ** -60
+
+
+@pytest.mark.parametrize("family", ["tight", "signed"])
+@pytest.mark.parametrize("M,Fd,K", DGRAD_CPU_SHAPES)
+def test_dgrad_swiglu_emulation_within_bounds(M, Fd, K, family):
+    inputs, (dg, bound_dg, du, bound_du) = _dgrad_case(M, Fd, K, family)
+    got_dg, got_du = R.dgrad_swiglu_emulated(*inputs)
+    for what, got, ref, bound in (("dg", got_dg, dg, bound_dg), ("du", got_du, du, bound_du)):
+        ratio = R.bound_ratio(got, ref, bound)
+        print(f"RATIO emulated dgrad[{M}x{Fd}x{K},{family}] {what} {ratio:.3g}")
+        assert ratio <= 1, f"{what}: error / bound = {ratio:.3g}"
+        if family == "tight":
+            loose = R.loose_fraction(ref, bound)
+            print(f"LOOSE dgrad[{M}x{Fd}x{K}] {what} {loose:.3f}")
+            assert loose <= 0.10, f"{what}: {loose:.3f} of the bounds are not bf16 rounding alone"
+
+
+@pytest.mark.parametrize("mutation", DGRAD_MUTATIONS)
+@pytest.mark.parametrize("M,Fd,K", DGRAD_CPU_SHAPES)
+def test_dgrad_swiglu_bounds_catch(M, Fd, K, mutation):
+    inputs, (dg, bound_dg, du, bound_du) = _dgrad_case(M, Fd, K, "tight")
+    got_dg, got_du = R.dgrad_swiglu_emulated(*inputs, mutation=mutation)
+    ratio = max(R.bound_ratio(got_dg, dg, bound_dg), R.bound_ratio(got_du, du, bound_du))
+    assert ratio > 1, f"{mutation} stays inside the bounds ({ratio:.3g})"
+
+
+@pytest.mark.parametrize("family", ["tight", "signed"])
+@pytest.mark.parametrize("M,Fd,K", W13_CPU_SHAPES)
+def test_w13_swiglu_emulation_within_bounds(M, Fd, K, family):
+    inputs, (gu, bound_gu, h, bound_h) = _w13_case(M, Fd, K, family)
+    got_gu, got_h = R.w13_swiglu_emulated(*inputs)
+    for what, got, ref, bound in (("gu", got_gu, gu, bound_gu), ("h", got_h, h, bound_h)):
+        ratio = R.bound_ratio(got, ref, bound)
+        print(f"RATIO emulated w13[{M}x{Fd}x{K},{family}] {what} {ratio:.3g}")
+        assert ratio <= 1, f"{what}: error / bound = {ratio:.3g}"
+        if family == "tight":
+            loose = R.loose_fraction(ref, bound)
+            print(f"LOOSE w13[{M}x{Fd}x{K}] {what} {loose:.3f}")
+            assert loose <= 0.10, f"{what}: {loose:.3f} of the bounds are not bf16 rounding alone"
+
+
+@pytest.mark.parametrize("mutation", W13_MUTATIONS)
+@pytest.mark.parametrize("M,Fd,K", W13_CPU_SHAPES)
+def test_w13_swiglu_bounds_catch(M, Fd, K, mutation):
+    inputs, (gu, bound_gu, h, bound_h) = _w13_case(M, Fd, K, "tight")
+    got_gu, got_h = R.w13_swiglu_emulated(*inputs, mutation=mutation)
+    ratio = max(R.bound_ratio(got_gu, gu, bound_gu), R.bound_ratio(got_h, h, bound_h))
+    assert ratio > 1, f"{mutation} stays inside the bounds ({ratio:.3g})"
 
 
 def test_ratio_helper_flags_nan_and_scales():
