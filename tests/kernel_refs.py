@@ -10,7 +10,9 @@ cancels).  ``tests/test_kernel_refs_cpu.py`` checks each form against
 
 The two bf16 GEMMs with a SwiGLU epilogue have their own section: closed forms
 computed on the CPU with a bound per element instead of ``mag``, the inputs the
-CPU and GPU tests share, and a float32 emulation of each epilogue.
+CPU and GPU tests share, and a float32 emulation of each epilogue.  The plain
+bf16 GEMMs and the RoPE-epilogue GEMM follow in the same form, with a third
+input family (sparse small integers) on which the output must be bit-equal.
 """
 from __future__ import annotations
 
@@ -289,6 +291,205 @@ def _swiglu_operands(gu, F, mutation):
     else:
         assert mutation in ("", "drop_last_ktile", "sigmoid_neg", "f_plus"), mutation
     return g, u
+
+
+# ---------------------------------- plain and RoPE-epilogue bf16 GEMMs ---
+# mxk_gemm_bf16_tn / _tn_variant / _ex* and mxk_gemm_bf16_rope: fp64 on the
+# CPU with a bound per element.  tests/test_gpu_gemm_numerics.py derives the
+# bounds; the shapes its cases use are listed here, so that
+# tests/test_kernel_refs_cpu.py checks the conditions on the inputs for
+# exactly those.
+GEMM_FAMILIES = ("tight", "signed", "exact")
+GEMM_A_ZERO = (5, 3)            # row m and column k of a
+GEMM_B_ZERO = (7, 3)            # row k and column n of b
+GEMM_EXACT_MAX_S = 256          # integers up to 2^8 are exact in bf16
+
+GEMM_TN_KS = (64, 128, 192, 256, 320, 384, 448, 832, 1216)   # 1-7, 13 and 19 K-tiles
+GEMM_TN_SHAPES = ((256, 256), (512, 768))
+GEMM_TN_XCD_SHAPE = (4096, 4096, 256)
+GEMM_STRIDED_SHAPE = (512, 768, 320)
+GEMM_GENERIC_SHAPES = ((1, 1, 1), (17, 33, 65), (255, 257, 63), (256, 256, 64))
+GEMM_EX_SHAPES = tuple((256, 512, K) for K in (64, 128, 256)) + \
+    tuple((512, 768, K) for K in (192, 320, 448, 1216))
+GEMM_EX_XCD_SHAPE = (4096, 4096, 192)
+GEMM_SPLIT_SHAPES = ((512, 768, 1024), (256, 256, 1024), (256, 256, 960))
+GEMM_ROPE_M, GEMM_ROPE_S = 512, 256
+GEMM_ROPE_COLS = ((1536, 1280), (1280, 1152))     # (N, rope_cols)
+GEMM_ROPE_KS = (64, 256, 320)
+GEMM_LINEAR_SHAPES = ((512, 768, 256), (512, 256, 768), (768, 256, 512))   # fwd, dgrad, wgrad
+GEMM_GPU_SHAPES = tuple(dict.fromkeys(
+    tuple((M, N, K) for M, N in GEMM_TN_SHAPES for K in GEMM_TN_KS) +
+    (GEMM_TN_XCD_SHAPE, GEMM_STRIDED_SHAPE) + GEMM_GENERIC_SHAPES + GEMM_EX_SHAPES +
+    (GEMM_EX_XCD_SHAPE,) + GEMM_SPLIT_SHAPES +
+    tuple((GEMM_ROPE_M, N, K) for N, _ in GEMM_ROPE_COLS for K in GEMM_ROPE_KS) + GEMM_LINEAR_SHAPES))
+
+
+def gemm_inputs(M: int, N: int, K: int, family: str, seed: int = 0):
+    """-> bf16 (a [M][K], b [K][N]).
+
+    tight / signed: magnitudes in [2^-4, 1.5), a's row r scaled
+    2^((r mod 9) - 4), b's column c scaled 2^((c mod 7) - 3) with a sign per
+    column; row GEMM_A_ZERO[0] and column GEMM_A_ZERO[1] of a, row
+    GEMM_B_ZERO[0] and column GEMM_B_ZERO[1] of b are zero (where the matrix
+    has more than 8 of them).  On tight a >= 0 and a column of b has one sign:
+    S = |d|.
+    exact: an entry is nonzero with probability min(1, sqrt(48 / K)), then
+    +-1 or +-2: every partial sum of a dot product is an integer of magnitude
+    at most S (asserted <= GEMM_EXACT_MAX_S by the callers), exact in fp32
+    and in bf16 in any order."""
+    assert family in GEMM_FAMILIES
+    if family == "exact":
+        gen = torch.Generator().manual_seed(1000 * seed + 902)
+        p = min(1.0, math.sqrt(48.0 / K))
+
+        def small(shape):
+            nz = (torch.rand(shape, generator=gen) < p).double()
+            mag = torch.where(torch.rand(shape, generator=gen) < 0.5, 1.0, 2.0).double()
+            return (nz * mag * _signs(shape, gen)).bfloat16()
+        return small((M, K)), small((K, N))
+    signed = family == "signed"
+    gen = torch.Generator().manual_seed(1000 * seed + 900 + (1 if signed else 0))
+    a = _operand((M, K), gen, signed) * _pow2(torch.arange(M), 9, 4)[:, None]
+    b = _operand((K, N), gen, signed) * (_pow2(torch.arange(N), 7, 3) * _signs(N, gen))[None, :]
+    for t, (r, c) in ((a, GEMM_A_ZERO), (b, GEMM_B_ZERO)):
+        if t.shape[0] > 8:
+            t[r] = 0
+        if t.shape[1] > 8:
+            t[:, c] = 0
+    return a.bfloat16(), b.bfloat16()
+
+
+def gemm_plain(a, b):
+    """a [M][K], b [K][N] -> (d, bound, S): d = a b in fp64 and
+    bound = 2^-8 |d| + K 2^-23 S + atol."""
+    d, S, delta = gemm_term(a, b)
+    d = d + 0.0                       # an exact zero is +0, as a sum that starts from +0
+    return d, 2.0 ** -8 * d.abs() + delta + GEMM_ATOL, S
+
+
+def worst_ratio(got, ref, bound):
+    """-> (largest |got - ref| / bound, its row, its column); NaN / inf in
+    ``got`` give inf at the first such element."""
+    got = got.detach().double().cpu()
+    bad = ~torch.isfinite(got)
+    ratio = torch.where(bad, torch.full_like(got, float("inf")), (got - ref).abs() / bound)
+    i = int(ratio.argmax())
+    return ratio.view(-1)[i].item(), i // ratio.shape[1], i % ratio.shape[1]
+
+
+def quarter_turn_tables(S: int, half: int = 64):
+    """-> fp32 (cos, sin) [S][half], each (position, frequency) one of the four
+    quarter turns (1, 0), (0, 1), (-1, 0), (0, -1), picked by a hash of both
+    indices: rotating exact integers by it is an exact signed permutation."""
+    pos, f = torch.arange(S, dtype=torch.int64)[:, None], torch.arange(half, dtype=torch.int64)[None, :]
+    h = (pos * 2654435761 + f * 2246822519 + 374761393) & 0xFFFFFFFF
+    h = ((h ^ (h >> 15)) * 2246822519) & 0xFFFFFFFF
+    turn = ((h ^ (h >> 13)) >> 7) & 3
+    cos = torch.tensor([1.0, 0.0, -1.0, 0.0])[turn]
+    sin = torch.tensor([0.0, 1.0, 0.0, -1.0])[turn]
+    return cos.contiguous(), sin.contiguous()
+
+
+def _rope_heads(x, rope_cols):
+    """x [M][N] -> (lo, hi) [M][heads][64] of the heads below rope_cols."""
+    v = x[:, :rope_cols].reshape(x.shape[0], rope_cols // 128, 2, 64)
+    return v[:, :, 0], v[:, :, 1]
+
+
+def gemm_rope(a, b, cos, sin, S: int, rope_cols: int):
+    """The RoPE-epilogue GEMM: d = a b, then in every 128-column head below
+    rope_cols, with (x, y) = d[.., i], d[.., i + 64] and (c, s) of row t at
+    table row t mod S:  x' = x c - y s,  y' = y c + x s (the fp32 tables are
+    exact inputs).  -> (ref, bound) in fp64; columns from rope_cols on carry
+    the plain GEMM and its bound."""
+    d, bound, _ = gemm_plain(a, b)
+    M = d.shape[0]
+    pos = torch.arange(M) % S
+    c = cos.detach().double().cpu()[pos][:, None, :]
+    s = sin.detach().double().cpu()[pos][:, None, :]
+    x, y = _rope_heads(d, rope_cols)
+    # what the bf16 rounding of the accumulators and their accumulation leave in x, y
+    ex, ey = (v - GEMM_ATOL for v in _rope_heads(bound, rope_cols))
+    rx = x * c + (-(y * s))           # the kernel's form: the same sign of an exact zero
+    ry = y * c + x * s
+    bx = (2.0 ** -8 * rx.abs() + c.abs() * ex + s.abs() * ey +
+          2.0 ** -23 * ((x * c).abs() + (y * s).abs()) + GEMM_ATOL)
+    by = (2.0 ** -8 * ry.abs() + c.abs() * ey + s.abs() * ex +
+          2.0 ** -23 * ((y * c).abs() + (x * s).abs()) + GEMM_ATOL)
+    ref, bnd = d.clone(), bound.clone()
+    ref[:, :rope_cols] = torch.stack([rx, ry], 2).reshape(M, rope_cols)
+    bnd[:, :rope_cols] = torch.stack([bx, by], 2).reshape(M, rope_cols)
+    return ref, bnd
+
+
+GEMM_MUTATIONS = ("drop_last_ktile", "drop_k", "dup_k", "swap_chunks", "stale_b", "transpose_c16",
+                  "split_half_twice")
+GEMM_ROPE_MUTATIONS = ("partner_32", "pos_off_64", "head_past")
+
+
+def gemm_emulated(a, b, mutation: str = "", split: bool = False):
+    """The kernels' arithmetic in float32 on the CPU: fp32 accumulation of
+    a [M][K] b [K][N] (``split``: two K halves accumulated apart, then added,
+    as the split tail's fixup does), fp32 result.  ``mutation`` plants one
+    defect, the single-k ones in rows 16-31 only (one fragment of one wave):
+    drop_last_ktile  the last 64 k are not accumulated
+    drop_k           k0 = K / 2 + 1 is skipped
+    dup_k            a[.., k0] is read again in place of a[.., k0 + 1]
+    swap_chunks      the 8-wide chunk of k0 exchanged between rows 16 and 17 of a
+    stale_b          the last K-tile multiplies the previous K-tile's b
+    transpose_c16    rows 32-47 x columns 16-31 of the result transposed
+    split_half_twice the fixup adds the first half's partial twice"""
+    a32, b32 = a.float().clone(), b.float().clone()
+    K = a32.shape[1]
+    k0 = K // 2 + 1
+    if mutation == "drop_last_ktile":
+        a32[:, K - 64:] = 0
+    elif mutation == "drop_k":
+        a32[16:32, k0] = 0
+    elif mutation == "dup_k":
+        a32[16:32, k0 + 1] = a32[16:32, k0]
+    elif mutation == "swap_chunks":
+        c0 = k0 // 8 * 8
+        a32[[16, 17], c0:c0 + 8] = a32[[17, 16], c0:c0 + 8]
+    elif mutation == "stale_b":
+        b32[K - 64:] = b32[K - 128:K - 64].clone()
+    else:
+        assert mutation in ("", "transpose_c16", "split_half_twice"), mutation
+    if split or mutation == "split_half_twice":
+        lo = a32[:, :K // 2] @ b32[:K // 2]
+        acc = lo + (lo if mutation == "split_half_twice" else a32[:, K // 2:] @ b32[K // 2:])
+    else:
+        acc = a32 @ b32
+    if mutation == "transpose_c16":
+        acc[32:48, 16:32] = acc[32:48, 16:32].t().clone()
+    return acc
+
+
+def gemm_rope_emulated(a, b, cos, sin, S: int, rope_cols: int, mutation: str = ""):
+    """mxk_gemm_bf16_rope in float32 on the CPU: the accumulators rounded to
+    bf16, then per lane its own 8 columns and the partner's 64 columns away,
+    x' = fma(x, c, -(y s)) and y' = fma(y, c, x s) in fp32 (the fma's one
+    rounding is made in fp64 here), rounded to bf16.  Mutations:
+    partner_32   the partner chunk is read 32 columns away
+    pos_off_64   the table row is that of the token 64 rows further down
+    head_past    one more head than rope_cols says is rotated"""
+    assert mutation in ("",) + GEMM_ROPE_MUTATIONS, mutation
+    out = gemm_emulated(a, b).bfloat16()
+    M, N = out.shape
+    cols = rope_cols + (128 if mutation == "head_past" else 0)
+    assert cols <= N
+    pos = (torch.arange(M) + (64 if mutation == "pos_off_64" else 0)) % S
+    col = torch.arange(128)
+    lo = col < 64
+    c = cos.float().cpu()[pos][:, None, :][..., col & 63]
+    s = sin.float().cpu()[pos][:, None, :][..., col & 63]
+    own = out[:, :cols].float().reshape(M, cols // 128, 128)
+    par = own[..., col ^ (32 if mutation == "partner_32" else 64)]
+    x, y = torch.where(lo, own, par), torch.where(lo, par, own)
+    rx = (x.double() * c.double() - (y * s).double()).float()
+    ry = (y.double() * c.double() + (x * s).double()).float()
+    out[:, :cols] = torch.where(lo, rx, ry).reshape(M, cols).bfloat16()
+    return out
 
 
 # ------------------------------------------------------------------- RoPE ---

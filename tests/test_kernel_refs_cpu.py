@@ -13,7 +13,27 @@ reciprocal, the same association, bf16 rounding): the emulation must stay
 inside the bounds on both input families, every planted defect must leave them
 on the tight family, and on the tight family the bound must be bf16 rounding
 and little else (``loose_fraction`` <= 10 %, from the reference alone).
-``tests/test_gpu_swiglu_gemm_numerics.py`` derives the bounds."""
+``tests/test_gpu_swiglu_gemm_numerics.py`` derives the bounds.
+
+The plain and the RoPE-epilogue GEMM (``gemm_plain``, ``gemm_rope``;
+``tests/test_gpu_gemm_numerics.py`` derives their bounds) are checked the same
+way, with the *exact* family next to tight and signed: the unmutated emulation
+is bit-equal on it, every planted defect changes bits, and the conditions the
+GPU tests assert from the reference alone (max S <= 256, ``loose_fraction``)
+hold for every shape they use.  Which family catches which planted defect
+(asserted at 1, 5, 16 and 19 K-tiles):
+
+  drop_last_ktile    tight (a whole K-tile is 5 % of |d| at K = 1216) and exact
+  drop_k, dup_k,     exact at every K (the one asserted); tight surely only
+  swap_chunks        while one term of K is above bf16 rounding (2^-8): at
+                     K = 1216 a term is 2^-10 |d| on average and tight sees
+                     it by luck, where an element's own rounding error is large
+  stale_b            tight and exact
+  transpose_c16      tight (row and column scales differ) and exact
+  split_half_twice   tight and exact
+  partner_32, pos_off_64, head_past
+                     exact with the quarter-turn table (bits), and signed with
+                     the model's tables (its bound)"""
 import functools
 
 import pytest
@@ -263,6 +283,157 @@ def test_w13_swiglu_bounds_catch(M, Fd, K, mutation):
     got_gu, got_h = R.w13_swiglu_emulated(*inputs, mutation=mutation)
     ratio = max(R.bound_ratio(got_gu, gu, bound_gu), R.bound_ratio(got_h, h, bound_h))
     assert ratio > 1, f"{mutation} stays inside the bounds ({ratio:.3g})"
+
+
+# ---- the plain and the RoPE-epilogue GEMM --------------------------------------
+# (the module docstring lists which family catches which planted defect)
+GEMM_CPU_SHAPES = [(256, 256, 64), (512, 768, 320), (256, 256, 1216)]
+GEMM_SINGLE_K = ("drop_k", "dup_k", "swap_chunks")
+
+
+@functools.lru_cache(maxsize=4)
+def _gemm_case(M, N, K, family):
+    a, b = R.gemm_inputs(M, N, K, family)
+    return (a, b), R.gemm_plain(a, b)
+
+
+def _bit_equal(got, ref):
+    return torch.equal(got.bfloat16().view(torch.int16), ref.bfloat16().view(torch.int16))
+
+
+def test_gemm_form_and_inputs():
+    a, b = _r((6, 12), 31), _r((12, 10), 32)
+    d, bound, S = R.gemm_plain(a, b)
+    _close(d, torch.einsum("mk,kn->mn", a, b), S, "d")
+    assert (bound >= 2.0 ** -8 * d.abs()).all()
+    a, b = R.gemm_inputs(256, 256, 64, "tight")
+    assert (a >= 0).all() and ((b >= 0).all(0) | (b <= 0).all(0)).all() and (b < 0).any() and (b > 0).any()
+    for family in ("tight", "signed"):
+        a, b = R.gemm_inputs(256, 256, 64, family)
+        assert not a[R.GEMM_A_ZERO[0]].any() and not a[:, R.GEMM_A_ZERO[1]].any()
+        assert not b[R.GEMM_B_ZERO[0]].any() and not b[:, R.GEMM_B_ZERO[1]].any()
+        nz = torch.cat([a[a != 0].abs().double(), b[b != 0].abs().double()])
+        # [2^-4, 1.5) times a scale in [2^-4, 2^4], rounded to bf16
+        assert nz.min() >= 2.0 ** -8 and nz.max() <= 1.5 * 2.0 ** 4
+    a, b = R.gemm_inputs(1, 1, 1, "signed")
+    assert a.item() != 0 and b.item() != 0
+    assert not torch.equal(R.gemm_inputs(256, 256, 64, "exact")[0],
+                           R.gemm_inputs(256, 256, 64, "exact", 1)[0])
+    cos, sin = R.quarter_turn_tables(256)
+    assert cos.dtype == torch.float32 and ((cos.abs() + sin.abs()) == 1).all() and (cos * sin == 0).all()
+    turns = (cos + 2 * sin).long()               # 1, 2, -1, -2
+    assert sorted(turns.unique().tolist()) == [-2, -1, 1, 2]
+    # rows and frequencies tell apart: no table row equals another, no column either
+    assert len({tuple(r.tolist()) for r in turns}) == 256
+    assert len({tuple(c.tolist()) for c in turns.t()}) == 64
+
+
+@pytest.mark.parametrize("M,N,K", R.GEMM_GPU_SHAPES)
+def test_gemm_input_conditions_of_every_gpu_shape(M, N, K):
+    """What tests/test_gpu_gemm_numerics.py asserts from the reference alone,
+    for every shape it uses: max S <= 256 on exact (with at least 18 nonzero
+    products per element and every k used, on the tiled shapes), and on tight
+    a bound that is bf16 rounding and little else."""
+    a, b = R.gemm_inputs(M, N, K, "exact")
+    S = a.float().abs() @ b.float().abs()        # integers below 2^24: exact in fp32
+    assert S.max().item() <= R.GEMM_EXACT_MAX_S, S.max().item()
+    if K >= 64:
+        used = (a != 0).float() @ (b != 0).float()
+        assert used.min().item() >= 18, used.min().item()
+        assert (a != 0).any(0).all() and (b != 0).any(1).all()
+    if M * N <= 512 * 1536:
+        a, b = R.gemm_inputs(M, N, K, "tight")
+        d, bound, S = R.gemm_plain(a, b)
+        assert torch.equal(S, d.abs())
+        assert R.loose_fraction(d, bound) <= 0.10
+
+
+@pytest.mark.parametrize("split", [False, True])
+@pytest.mark.parametrize("family", R.GEMM_FAMILIES)
+@pytest.mark.parametrize("M,N,K", GEMM_CPU_SHAPES + [(256, 256, 1024)])
+def test_gemm_emulation_within_bounds(M, N, K, family, split):
+    (a, b), (d, bound, S) = _gemm_case(M, N, K, family)
+    got = R.gemm_emulated(a, b, split=split).bfloat16()
+    ratio, r, c = R.worst_ratio(got, d, bound)
+    print(f"RATIO emulated gemm[{M}x{N}x{K},{family},split{int(split)}] {ratio:.3g}")
+    assert ratio <= 1, f"error / bound = {ratio:.3g} at ({r}, {c})"
+    if family == "exact":
+        assert S.max().item() <= R.GEMM_EXACT_MAX_S and _bit_equal(got, d)
+
+
+def _gemm_caught(M, N, K, family, mutation):
+    (a, b), (d, bound, _) = _gemm_case(M, N, K, family)
+    got = R.gemm_emulated(a, b, mutation=mutation).bfloat16()
+    return not _bit_equal(got, d) if family == "exact" else R.bound_ratio(got, d, bound) > 1
+
+
+# one K-tile has no previous stage whose b could be stale
+@pytest.mark.parametrize("M,N,K,mutation", [(*s, m) for s in GEMM_CPU_SHAPES + [(256, 256, 1024)]
+                                            for m in R.GEMM_MUTATIONS if not (m == "stale_b" and s[2] < 128)])
+def test_gemm_checks_catch(M, N, K, mutation):
+    caught = {f: _gemm_caught(M, N, K, f, mutation) for f in R.GEMM_FAMILIES}
+    print(f"CAUGHT gemm[{M}x{N}x{K}] {mutation} {caught}")
+    assert caught["exact"], f"{mutation}: bit-equal on exact"
+    # a single term of K = 1216 is 2^-10 |d| on average, under bf16 rounding:
+    # tight sees it only where it meets an element whose rounding error is
+    # already near the bound, so nothing is asserted of tight there
+    if mutation not in GEMM_SINGLE_K:
+        assert caught["tight"], f"{mutation}: inside the bound on tight"
+
+
+@functools.lru_cache(maxsize=None)
+def _rope_tables(kind):
+    if kind == "quarter":
+        return R.quarter_turn_tables(R.GEMM_ROPE_S)
+    from mxk8s.ops.fused import rope_tables
+    return rope_tables(R.GEMM_ROPE_S, 128)
+
+
+@functools.lru_cache(maxsize=4)
+def _rope_case(N, rope_cols, K, family):
+    a, b = R.gemm_inputs(R.GEMM_ROPE_M, N, K, family)
+    cos, sin = _rope_tables("quarter" if family == "exact" else "real")
+    return (a, b, cos, sin), R.gemm_rope(a, b, cos, sin, R.GEMM_ROPE_S, rope_cols)
+
+
+def test_gemm_rope_form():
+    """gemm_rope is the rotate-half form of ``rope`` (checked against the
+    complex product above) applied to the heads below rope_cols."""
+    M, N, K, S, rope_cols = 8, 384, 12, 4, 256
+    a, b = _r((M, K), 41), _r((K, N), 42)
+    ang = _r((S, 64), 43) * 3
+    ref, bound = R.gemm_rope(a, b, ang.cos(), ang.sin(), S, rope_cols)
+    d = a @ b
+    want, mag = R.rope(d[:, :rope_cols].reshape(M, 2, 128), ang.cos(), ang.sin(), 1.0, S)
+    _close(ref[:, :rope_cols], want.reshape(M, rope_cols), mag.reshape(M, rope_cols), "rope of d")
+    assert torch.equal(ref[:, rope_cols:], d[:, rope_cols:] + 0.0)
+    assert (bound >= 2.0 ** -8 * ref.abs()).all()
+
+
+@pytest.mark.parametrize("family", R.GEMM_FAMILIES)
+@pytest.mark.parametrize("K", [64, 320])
+@pytest.mark.parametrize("N,rope_cols", R.GEMM_ROPE_COLS)
+def test_gemm_rope_emulation_within_bounds(N, rope_cols, K, family):
+    inputs, (ref, bound) = _rope_case(N, rope_cols, K, family)
+    got = R.gemm_rope_emulated(*inputs, R.GEMM_ROPE_S, rope_cols)
+    ratio, r, c = R.worst_ratio(got, ref, bound)
+    print(f"RATIO emulated rope[{N}/{rope_cols}x{K},{family}] {ratio:.3g}")
+    assert ratio <= 1, f"error / bound = {ratio:.3g} at ({r}, {c})"
+    if family == "exact":
+        assert _bit_equal(got, ref)
+
+
+@pytest.mark.parametrize("mutation", R.GEMM_ROPE_MUTATIONS)
+@pytest.mark.parametrize("K", [64, 320])
+@pytest.mark.parametrize("N,rope_cols", R.GEMM_ROPE_COLS)
+def test_gemm_rope_checks_catch(N, rope_cols, K, mutation):
+    caught = {}
+    for family in ("signed", "exact"):
+        inputs, (ref, bound) = _rope_case(N, rope_cols, K, family)
+        got = R.gemm_rope_emulated(*inputs, R.GEMM_ROPE_S, rope_cols, mutation=mutation)
+        caught[family] = not _bit_equal(got, ref) if family == "exact" else R.bound_ratio(got, ref, bound) > 1
+    print(f"CAUGHT rope[{N}/{rope_cols}x{K}] {mutation} {caught}")
+    assert caught["exact"] and caught["signed"], caught
 
 
 def test_ratio_helper_flags_nan_and_scales():
