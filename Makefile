@@ -36,7 +36,7 @@ KERNEL_SRCS := native/kernels/gemm_bf16.hip native/kernels/vector_add.hip \
                native/kernels/fused_ops.hip native/kernels/optim.hip native/kernels/attention_fwd.hip native/kernels/attention_bwd.hip native/kernels/attention_bwd256.hip native/kernels/attention_fwd256.hip native/kernels/attention_dq256.hip \
                native/kernels/gemm_bf16_layouts.hip native/kernels/xent.hip native/kernels/contention.hip \
                native/kernels/gemm_mxfp8.hip native/kernels/gemm_mxfp4.hip \
-               native/kernels/quantize_mxfp4_sr.hip
+               native/kernels/quantize_mxfp4_sr.hip native/kernels/swiglu_quantize_mx.hip
 KERNEL_OBJS := $(patsubst native/kernels/%.hip,$(BUILD)/kernels/%.o,$(KERNEL_SRCS))
 EXP_SRCS    := $(KERNEL_SRCS) $(wildcard native/kernels/experiments/*.hip)
 EXP_OBJS    := $(patsubst native/kernels/%.hip,$(BUILD)/exp/%.o,$(EXP_SRCS))

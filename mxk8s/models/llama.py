@@ -29,7 +29,9 @@ import torch.nn.functional as F
 
 from ..ops.attention import (flash_attention, proj_rope_attention, qkv_rope_attention,
                               supported as flash_supported)
-from ..ops.linear import GRAD_ROUNDINGS, Linear, SwiGLULinear, swiglu_mlp
+from ..ops import linear as _linear
+from ..ops.linear import (GRAD_ROUNDINGS, Linear, SwiGLULinear, is_mxfp8_linear_shape, swiglu_mlp,
+                          swiglu_mlp_mx)
 from ..ops.xent import cross_entropy
 from ..ops.embedding import Embedding
 from ..ops.fused import add_rmsnorm, qkv_rope, rmsnorm, rope_tables
@@ -177,6 +179,16 @@ class MLP(nn.Module):
             # one node: up-projection with SwiGLU in its epilogue, down
             # projection, fused dgrad-SwiGLU backward (mxk8s.ops.linear)
             return swiglu_mlp(x, self.w13.weight, self.w2.weight)
+        w13, w2 = self.w13, self.w2
+        if x.is_cuda and x.dtype == torch.bfloat16 and w13.compute != "bf16" and \
+                (w2.compute, w2.grad_rounding) == (w13.compute, w13.grad_rounding) and \
+                _linear._USE_MX_FUSED_SWIGLU:
+            # an MX format: one node again, SwiGLU and its gradient inside the
+            # quantisers; bit for bit the composition below (MXK_MX_FUSED_SWIGLU=0)
+            T = x.numel() // w13.in_features
+            if is_mxfp8_linear_shape(T, w13.in_features, w13.out_features) and \
+                    is_mxfp8_linear_shape(T, w2.in_features, w2.out_features):
+                return swiglu_mlp_mx(x, w13.weight, w2.weight, w13.compute, w13.grad_rounding)
         return self.w2(self.w13(x))
 
 

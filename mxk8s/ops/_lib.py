@@ -66,6 +66,15 @@ _SIGNATURES = {
     "mxk_quantize_mxfp4_sr": (_i, [_vp, _vp, _vp, _l, _i, _l, _l, _l, _u64, _vp]),
     "mxk_quantize_mxfp4_sr_t": (_i, [_vp, _vp, _vp, _l, _l, _l, _l, _l, _u64, _vp]),
     "mxk_quantize_mxfp4_sr_dual": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _l, _u64, _vp]),
+    # SwiGLU inside the MX quantisers (swiglu_quantize_mx.hip): gu [T, 2F] -> the images of
+    # h [T, F]; gu and dh [T, F] -> both images of dgu [T, 2F]
+    "mxk_swiglu_quantize_mxfp8": (_i, [_vp, _vp, _vp, _l, _l, _l, _l, _l, _vp]),
+    "mxk_swiglu_quantize_mxfp8_t": (_i, [_vp, _vp, _vp, _l, _l, _l, _l, _l, _vp]),
+    "mxk_swiglu_bwd_quantize_mxfp8_dual": (_i, [_vp] * 6 + [_l] * 8 + [_vp]),
+    "mxk_swiglu_quantize_mxfp4": (_i, [_vp, _vp, _vp, _l, _l, _l, _l, _l, _vp]),
+    "mxk_swiglu_quantize_mxfp4_t": (_i, [_vp, _vp, _vp, _l, _l, _l, _l, _l, _vp]),
+    "mxk_swiglu_bwd_quantize_mxfp4_dual": (_i, [_vp] * 6 + [_l] * 8 + [_vp]),
+    "mxk_swiglu_bwd_quantize_mxfp4_sr_dual": (_i, [_vp] * 6 + [_l] * 8 + [_u64, _vp]),
     "mxk_gemm_bf16_ex": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "mxk_gemm_bf16_ex_variant": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "mxk_gemm_bf16_ex_ws": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _l,

@@ -121,6 +121,121 @@ def quantize_dual(name: str, per_byte: int, dtype: torch.dtype, ref: Callable, x
     return q, s, qt, st
 
 
+# ---- SwiGLU inside the quantisers (native/kernels/swiglu_quantize_mx.hip) ---------
+# gu = [g | u] is [T, 2F]; the images are those of h = silu(g) * u [T, F] or of
+# dgu = [dg | du] [T, 2F].  The kernels take 16-B aligned rows only; every other
+# tensor (CPU tensors among them) gets the composition of the stand-alone ops,
+# which the kernels equal bit for bit on the GPU.
+_TR_MAX_F = 64 * 65535          # grid.y of the transposing kernels
+
+
+def check_gu(gu: torch.Tensor, rows32: bool, dh=None, with_dh: bool = False) -> None:
+    """The argument of a fused SwiGLU quantiser, [T, 2F]; with_dh: and dh [T, F]."""
+    if not isinstance(gu, torch.Tensor):
+        raise TypeError("gu must be a tensor")
+    if gu.dtype != torch.bfloat16:
+        raise TypeError(f"gu must be bfloat16, got {gu.dtype}")
+    if gu.dim() != 2:
+        raise ValueError(f"gu must be 2-D, got shape {tuple(gu.shape)}")
+    T, F2 = gu.shape
+    if T == 0 or F2 == 0 or F2 % (2 * BLOCK) or (rows32 and T % BLOCK):
+        raise ValueError(f"gu must be [T, 2F] with F a positive multiple of {BLOCK} and T "
+                         + (f"a positive multiple of {BLOCK}" if rows32 else "> 0")
+                         + f", got {tuple(gu.shape)}")
+    if gu.stride(1) != 1:
+        raise ValueError("gu must be row-major (stride(1) == 1)")
+    if not with_dh:
+        return
+    if not isinstance(dh, torch.Tensor):
+        raise TypeError("dh must be a tensor")
+    if dh.dtype != torch.bfloat16:
+        raise TypeError(f"dh must be bfloat16, got {dh.dtype}")
+    if dh.dim() != 2 or tuple(dh.shape) != (T, F2 // 2):
+        raise ValueError(f"dh must be [{T}, {F2 // 2}], got {tuple(dh.shape)}")
+    if dh.stride(1) != 1:
+        raise ValueError("dh must be row-major (stride(1) == 1)")
+    if dh.device != gu.device:
+        raise ValueError("gu and dh are on different devices")
+
+
+def _swiglu_h(gu: torch.Tensor) -> torch.Tensor:
+    from .fused import swiglu_fwd, swiglu_ref
+    return swiglu_ref(gu) if gu.device.type == "cpu" else swiglu_fwd(gu)
+
+
+def _swiglu_dgu(gu: torch.Tensor, dh: torch.Tensor) -> torch.Tensor:
+    from .fused import swiglu_bwd, swiglu_bwd_ref
+    return swiglu_bwd_ref(gu, dh) if gu.device.type == "cpu" else swiglu_bwd(gu, dh)
+
+
+def _ld(t: torch.Tensor) -> int:
+    """The row stride handed to a kernel: that of a single row is never used and
+    may be anything in torch, so its width stands for it."""
+    return t.stride(0) if t.shape[0] > 1 else t.shape[1]
+
+
+def _kernel_takes(*tensors: torch.Tensor) -> bool:
+    """GPU tensors with 16-B aligned rows that do not overlap (the fused kernels
+    have no by-element form, and refuse a row stride below the width, such as
+    an expanded tensor's 0)."""
+    return all(t.is_cuda and t.data_ptr() % 16 == 0 and _ld(t) % 8 == 0 and _ld(t) >= t.shape[1]
+               for t in tensors)
+
+
+def swiglu_quantize_rows(name: str, per_byte: int, dtype: torch.dtype, quantize: Callable,
+                         gu: torch.Tensor):
+    """``swiglu_quantize_<name>``: ``quantize`` is the format's ``quantize_<name>``."""
+    check_gu(gu, rows32=False)
+    if not _kernel_takes(gu):
+        return quantize(_swiglu_h(gu))
+    T, F = gu.shape[0], gu.shape[1] // 2
+    q = torch.empty((T, F // per_byte), dtype=dtype, device=gu.device)
+    s = torch.empty((T, F // BLOCK), dtype=torch.uint8, device=gu.device)
+    fn = f"mxk_swiglu_quantize_{name}"
+    rc = getattr(_lib.lib(), fn)(gu.data_ptr(), q.data_ptr(), s.data_ptr(), T, F, _ld(gu),
+                                 q.stride(0), s.stride(0), _lib.stream_ptr(gu.device))
+    _lib.check(rc, fn)
+    return q, s
+
+
+def swiglu_quantize_t(name: str, per_byte: int, dtype: torch.dtype, quantize_t: Callable,
+                      gu: torch.Tensor):
+    """``swiglu_quantize_<name>_t``: ``quantize_t`` is the format's ``quantize_<name>_t``."""
+    check_gu(gu, rows32=True)
+    T, F = gu.shape[0], gu.shape[1] // 2
+    if not _kernel_takes(gu) or F > _TR_MAX_F:
+        return quantize_t(_swiglu_h(gu))
+    qt = torch.empty((F, T // per_byte), dtype=dtype, device=gu.device)
+    st = torch.empty((F, T // BLOCK), dtype=torch.uint8, device=gu.device)
+    fn = f"mxk_swiglu_quantize_{name}_t"
+    rc = getattr(_lib.lib(), fn)(gu.data_ptr(), qt.data_ptr(), st.data_ptr(), T, F, _ld(gu),
+                                 qt.stride(0), st.stride(0), _lib.stream_ptr(gu.device))
+    _lib.check(rc, fn)
+    return qt, st
+
+
+def swiglu_bwd_quantize_dual(name: str, per_byte: int, dtype: torch.dtype, quantize_dual: Callable,
+                             gu: torch.Tensor, dh: torch.Tensor, seed: int | None = None):
+    """``swiglu_bwd_quantize_<name>_dual``: ``quantize_dual`` is the format's
+    ``quantize_<name>_dual``; a ``seed`` selects stochastic rounding."""
+    check_gu(gu, rows32=True, dh=dh, with_dh=True)
+    sr, ref_args, seed_arg = _sr(seed)
+    T, F = gu.shape[0], gu.shape[1] // 2
+    if not _kernel_takes(gu, dh) or F > _TR_MAX_F or (seed is not None and max(T, 2 * F) >= 2 ** 32):
+        return quantize_dual(_swiglu_dgu(gu, dh), *ref_args)
+    q = torch.empty((T, 2 * F // per_byte), dtype=dtype, device=gu.device)
+    s = torch.empty((T, 2 * F // BLOCK), dtype=torch.uint8, device=gu.device)
+    qt = torch.empty((2 * F, T // per_byte), dtype=dtype, device=gu.device)
+    st = torch.empty((2 * F, T // BLOCK), dtype=torch.uint8, device=gu.device)
+    fn = f"mxk_swiglu_bwd_quantize_{name}{sr}_dual"
+    rc = getattr(_lib.lib(), fn)(gu.data_ptr(), dh.data_ptr(), q.data_ptr(), s.data_ptr(),
+                                 qt.data_ptr(), st.data_ptr(), T, F, _ld(gu), _ld(dh),
+                                 q.stride(0), s.stride(0), qt.stride(0), st.stride(0), *seed_arg,
+                                 _lib.stream_ptr(gu.device))
+    _lib.check(rc, fn)
+    return q, s, qt, st
+
+
 def check_pair(q: torch.Tensor, s: torch.Tensor, qn: str, sn: str, dtype: torch.dtype, wording: str,
                per_byte: int) -> None:
     """``q`` holds ``per_byte`` elements in each item of ``dtype``; ``wording``

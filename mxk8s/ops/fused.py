@@ -26,6 +26,15 @@ def swiglu_ref(gu: torch.Tensor) -> torch.Tensor:
     return (torch.nn.functional.silu(g) * u).to(gu.dtype)
 
 
+def swiglu_bwd_ref(gu: torch.Tensor, dh: torch.Tensor) -> torch.Tensor:
+    """d[g | u] of h = silu(g) * u: dg = dh u s (1 + g (1 - s)), du = dh g s with
+    s = sigmoid(g), in fp32, output in gu's dtype."""
+    g, u = gu.float().chunk(2, dim=-1)
+    d = dh.float()
+    s = torch.sigmoid(g)
+    return torch.cat([d * u * s * (1 + g * (1 - s)), d * g * s], dim=-1).to(gu.dtype)
+
+
 def rope_tables(seq_len: int, head_dim: int, theta: float = 500000.0,
                 device=None) -> tuple[torch.Tensor, torch.Tensor]:
     """cos/sin tables [S, D/2] fp32 (host-precomputed; no device trig)."""

@@ -190,34 +190,41 @@ def _mx_forward(fmt: str, ctx, x, weight):
     return y.to(x.dtype).view(*x.shape[:-1], weight.shape[0])
 
 
+def _mx_grad_images(fmt: str, dy2, need_rows: bool, need_t: bool, sr_seed=None):
+    """((q, s) or None, (qt, st) or None) of an output gradient: the row image for
+    the input gradient, the transposed one for the weight gradient, from one
+    read when both are needed.  sr_seed (MXFP4): stochastic rounding, the row
+    image with this seed and the transposed image with the next one, whichever
+    of the two a call needs."""
+    _, quantize, quantize_t, quantize_dual = _mx_ops(fmt)
+    sr = () if sr_seed is None else ("stochastic", sr_seed)
+    if need_rows and need_t:
+        dq, ds, dqt, dst = quantize_dual(dy2, *sr)
+        return (dq, ds), (dqt, dst)
+    if need_rows:
+        return quantize(dy2, *sr), None
+    if need_t:
+        if sr_seed is not None:
+            return None, quantize_t(dy2, "stochastic", (sr_seed + 1) % 2 ** 64)
+        return None, quantize_t(dy2)
+    return None, None
+
+
 def _mx_backward(fmt: str, ctx, dy, sr_seed=None):
-    """sr_seed (MXFP4): dy is quantised with stochastic rounding, its row image
-    with this seed and its transposed image with the next one, whichever of
-    the two a call needs; W^T and x^T stay round-to-nearest."""
-    gemm, quantize, quantize_t, quantize_dual = _mx_ops(fmt)
+    """sr_seed (MXFP4): dy is quantised with stochastic rounding
+    (_mx_grad_images); W^T and x^T stay round-to-nearest."""
+    gemm, _, quantize_t, _ = _mx_ops(fmt)
     x, weight = ctx.saved_tensors
     need_x, need_w = ctx.needs_input_grad[:2]
     dy2 = _bf16_rows(dy.reshape(-1, dy.shape[-1]))
-    if sr_seed is not None:
-        if need_x and need_w:
-            dq, ds, dqt, dst = quantize_dual(dy2, "stochastic", sr_seed)
-        elif need_x:
-            dq, ds = quantize(dy2, "stochastic", sr_seed)
-        elif need_w:
-            dqt, dst = quantize_t(dy2, "stochastic", (sr_seed + 1) % 2 ** 64)
-    elif need_x and need_w:
-        dq, ds, dqt, dst = quantize_dual(dy2)
-    elif need_x:
-        dq, ds = quantize(dy2)
-    elif need_w:
-        dqt, dst = quantize_t(dy2)
+    rows, cols = _mx_grad_images(fmt, dy2, need_x, need_w, sr_seed)
     dx = dw = None
     if need_x:
-        dx = gemm(dq, ds, *quantize_t(_bf16_rows(weight)))
+        dx = gemm(*rows, *quantize_t(_bf16_rows(weight)))
         dx = dx.to(x.dtype).view(x.shape)
     if need_w:
         x2 = _bf16_rows(x.reshape(-1, x.shape[-1]))
-        dw = _mx_weight_grad(weight, (dqt, dst), quantize_t(x2), gemm)
+        dw = _mx_weight_grad(weight, cols, quantize_t(x2), gemm)
     return dx, dw
 
 
@@ -425,6 +432,129 @@ class _SwiGLUMLPFn(torch.autograd.Function):
 
 def swiglu_mlp(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor) -> torch.Tensor:
     return _SwiGLUMLPFn.apply(x, w13, w2)
+
+
+# ---- the MX MLP as one node ------------------------------------------------------
+# w2(swiglu(w13(x))) on an MX format as two Linear nodes writes h = swiglu(gu)
+# and dgu to HBM as bf16 only for a quantiser to read them back (h twice), and
+# saves h beside gu.  Here SwiGLU and its backward run inside the quantisers
+# (swiglu_quantize_<fmt>, .._t, swiglu_bwd_quantize_<fmt>_dual), whose images
+# equal the composition's bit for bit, so the node computes what the two
+# Linear nodes compute, bit for bit, with 3 launches and one saved [T, F]
+# tensor less per layer.  MXK_MX_FUSED_SWIGLU=0 runs the two nodes;
+# profiles/mx_swiglu/ has the measurement the default rests on.
+MX_FUSED_SWIGLU_DEFAULT = "1"
+
+
+def _mx_fused_swiglu_env(environ=os.environ) -> bool:
+    return environ.get("MXK_MX_FUSED_SWIGLU", MX_FUSED_SWIGLU_DEFAULT) != "0"
+
+
+_USE_MX_FUSED_SWIGLU = _mx_fused_swiglu_env()
+
+
+def _mx_swiglu_ops(fmt: str):
+    """(swiglu_quantize, swiglu_quantize_t, swiglu_bwd_quantize_dual) of "mxfp8" /
+    "mxfp4", read from the format's module at every call, as _mx_ops."""
+    if fmt == "mxfp8":
+        from . import mxfp8 as m
+    else:
+        from . import mxfp4 as m
+    return tuple(getattr(m, n.format(fmt)) for n in ("swiglu_quantize_{}", "swiglu_quantize_{}_t",
+                                                     "swiglu_bwd_quantize_{}_dual"))
+
+
+class _SwiGLUMLPMxFn(torch.autograd.Function):
+    """y = swiglu(x W13^T) W2^T with all five products on an MX GEMM: the MX twin
+    of _SwiGLUMLPFn.  Saves x, gu and the weights, not h.  seeds: None for
+    round-to-nearest gradients, else (w13's, w2's) of the stochastic quantisers
+    of dgu and dy, or () to draw them here from mxfp4.sr_next(), w13's first,
+    the order in which the two Linear calls draw them."""
+
+    @staticmethod
+    def forward(ctx, x, w13, w2, fmt, seeds):
+        gemm, quantize, _, _ = _mx_ops(fmt)
+        swiglu_quantize = _mx_swiglu_ops(fmt)[0]
+        if seeds == ():
+            from .mxfp4 import sr_next
+            seeds = (sr_next(), sr_next())
+        x2 = _bf16_rows(x.reshape(-1, x.shape[-1]))
+        gu = gemm(*quantize(x2), *quantize(_bf16_rows(w13)))
+        y = gemm(*swiglu_quantize(gu), *quantize(_bf16_rows(w2)))
+        ctx.save_for_backward(x2, gu, w13, w2)
+        ctx.fmt, ctx.seeds, ctx.xshape, ctx.xdtype = fmt, seeds, x.shape, x.dtype
+        return y.to(x.dtype).view(*x.shape[:-1], w2.shape[0])
+
+    @staticmethod
+    def backward(ctx, dy):
+        fmt = ctx.fmt
+        gemm, _, quantize_t, _ = _mx_ops(fmt)
+        _, swiglu_quantize_t, swiglu_bwd_quantize_dual = _mx_swiglu_ops(fmt)
+        x2, gu, w13, w2 = ctx.saved_tensors
+        need_x, need_w13, need_w2 = ctx.needs_input_grad[:3]
+        need_gu = need_x or need_w13
+        seed13, seed2 = ctx.seeds or (None, None)
+        dy2 = _bf16_rows(dy.reshape(-1, dy.shape[-1]))
+        rows, cols = _mx_grad_images(fmt, dy2, need_gu, need_w2, seed2)
+        dx = dw13 = dw2 = None
+        if need_gu:
+            dh = gemm(*rows, *quantize_t(_bf16_rows(w2)))
+        if need_w2:                              # W2's first, as autograd orders the two nodes
+            dw2 = _mx_weight_grad(w2, cols, swiglu_quantize_t(gu), gemm)
+        if need_gu:
+            # both images of dgu even where one gradient is not needed: each is
+            # the image the one-sided quantiser would draw (seed, seed + 1)
+            sr = () if seed13 is None else ("stochastic", seed13)
+            gq, gs, gqt, gst = swiglu_bwd_quantize_dual(gu, dh, *sr)
+            del dh
+            if need_x:
+                dx = gemm(gq, gs, *quantize_t(_bf16_rows(w13)))
+                dx = dx.to(ctx.xdtype).view(ctx.xshape)
+            if need_w13:
+                dw13 = _mx_weight_grad(w13, (gqt, gst), quantize_t(x2), gemm)
+        return dx, dw13, dw2, None, None
+
+
+def swiglu_mlp_mx(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor, fmt: str,
+                  grad_rounding: str = "nearest", seeds=None) -> torch.Tensor:
+    """``swiglu(x @ w13.T) @ w2.T`` (``w13`` ``[2F, in]`` = [gate | up], ``w2``
+    ``[out, F]``) as one autograd node whose five products run on the MX GEMM of
+    ``fmt`` (``"mxfp8"`` / ``"mxfp4"``): what ``Linear(compute=fmt)`` followed by
+    ``SwiGLULinear(compute=fmt)`` computes, bit for bit, with SwiGLU and its
+    gradient computed inside the quantisers, so neither ``swiglu(gu)`` nor
+    ``d(gu)`` is written as bf16 and ``swiglu(gu)`` is not saved.  The weight
+    gradients keep the ``main_grad`` contract of :class:`Linear`, ``w2``'s first.
+
+    ``grad_rounding="stochastic"`` (MXFP4 only) rounds ``dy`` and ``d(gu)``
+    stochastically; ``seeds`` is ``(w13's, w2's)``, or ``None`` to draw two from
+    ``mxfp4.sr_next()`` at forward time, ``w13``'s first.  Raises ``ValueError``
+    unless :func:`is_mxfp8_linear_shape` holds for both layers."""
+    if fmt not in ("mxfp8", "mxfp4"):
+        raise ValueError(f"fmt must be \"mxfp8\" or \"mxfp4\", got {fmt!r}")
+    _check_grad_rounding(grad_rounding)
+    if grad_rounding != "nearest" and fmt != "mxfp4":
+        raise ValueError(f"grad_rounding={grad_rounding!r} needs fmt=\"mxfp4\", got {fmt!r}")
+    if seeds is not None:
+        if grad_rounding != "stochastic":
+            raise ValueError("seeds are only taken with grad_rounding=\"stochastic\"")
+        if not isinstance(seeds, (tuple, list)) or len(seeds) != 2:
+            raise ValueError(f"seeds must be (w13's, w2's), got {seeds!r}")
+        for seed in seeds:
+            _check_grad_rounding(grad_rounding, seed)
+        seeds = tuple(seeds)
+    elif grad_rounding == "stochastic":
+        seeds = ()
+    if w13.dim() != 2 or w2.dim() != 2 or x.dim() < 1 or x.shape[-1] != w13.shape[1] or \
+            w13.shape[0] != 2 * w2.shape[1]:
+        raise ValueError(f"swiglu_mlp_mx: x {tuple(x.shape)}, w13 {tuple(w13.shape)} and w2 "
+                         f"{tuple(w2.shape)} do not match")
+    T = x.numel() // x.shape[-1] if x.shape[-1] else 0
+    if not (is_mxfp8_linear_shape(T, w13.shape[1], w13.shape[0]) and
+            is_mxfp8_linear_shape(T, w2.shape[1], w2.shape[0])):
+        raise ValueError(f"swiglu_mlp_mx needs tokens, in, ffn and out features to be positive "
+                         f"multiples of {_MX_TILE}, got T={T} in={w13.shape[1]} "
+                         f"ffn={w2.shape[1]} out={w2.shape[0]}")
+    return _SwiGLUMLPMxFn.apply(x, w13, w2, fmt, seeds)
 
 
 class Linear(nn.Linear):

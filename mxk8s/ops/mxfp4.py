@@ -192,6 +192,32 @@ def quantize_mxfp4_dual(x: torch.Tensor, rounding: str = "nearest",
                              check_rounding(rounding, seed))
 
 
+def swiglu_quantize_mxfp4(gu: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """``quantize_mxfp4(h)`` of ``h = silu(g) * u`` for bf16 ``gu = [g | u]``
+    ``[T, 2F]`` (``F % 32 == 0``), bit for bit, without ``h`` in memory: one kernel
+    (``native/kernels/swiglu_quantize_mx.hip``) for GPU tensors with 16-byte
+    aligned rows, the composition of the two ops for every other tensor."""
+    return _mx.swiglu_quantize_rows("mxfp4", 2, torch.uint8, quantize_mxfp4, gu)
+
+
+def swiglu_quantize_mxfp4_t(gu: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """``quantize_mxfp4_t(h)`` of ``h = silu(g) * u`` (``T % 32 == 0`` as well); see
+    :func:`swiglu_quantize_mxfp4`."""
+    return _mx.swiglu_quantize_t("mxfp4", 2, torch.uint8, quantize_mxfp4_t, gu)
+
+
+def swiglu_bwd_quantize_mxfp4_dual(gu: torch.Tensor, dh: torch.Tensor, rounding: str = "nearest",
+                                   seed: int | None = None):
+    """``quantize_mxfp4_dual(dgu, rounding, seed)`` of the SwiGLU gradient ``dgu =
+    [dg | du]`` ``[T, 2F]`` for ``gu`` ``[T, 2F]`` and ``dh`` ``[T, F]`` (bf16, ``T``
+    and ``F`` multiples of 32), bit for bit, from one read of ``gu`` and ``dh`` and
+    without ``dgu`` in memory.  Stochastic rounding draws by the coordinates of
+    ``dgu``'s images, the row image with ``seed`` and the transposed one with
+    ``seed + 1``; see :func:`swiglu_quantize_mxfp4`."""
+    return _mx.swiglu_bwd_quantize_dual("mxfp4", 2, torch.uint8, quantize_mxfp4_dual, gu, dh,
+                                        check_rounding(rounding, seed))
+
+
 # ---- seeds of the stochastic gradient quantisers ---------------------------------
 # One seed per linear_mxfp4 call (mxk8s.ops.linear): the n-th draw after
 # sr_reseed(seed, rank, step) is ((w1 << 32) | w0) & ~1 with w0, w1 the first

@@ -76,6 +76,28 @@ def quantize_mxfp8_dual(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor, to
     return _mx.quantize_dual("mxfp8", 1, torch.float8_e4m3fn, quantize_mxfp8_ref, x)
 
 
+def swiglu_quantize_mxfp8(gu: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """``quantize_mxfp8(h)`` of ``h = silu(g) * u`` for bf16 ``gu = [g | u]``
+    ``[T, 2F]`` (``F % 32 == 0``), bit for bit, without ``h`` in memory: one kernel
+    (``native/kernels/swiglu_quantize_mx.hip``) for GPU tensors with 16-byte
+    aligned rows, the composition of the two ops for every other tensor."""
+    return _mx.swiglu_quantize_rows("mxfp8", 1, torch.float8_e4m3fn, quantize_mxfp8, gu)
+
+
+def swiglu_quantize_mxfp8_t(gu: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """``quantize_mxfp8_t(h)`` of ``h = silu(g) * u`` (``T % 32 == 0`` as well); see
+    :func:`swiglu_quantize_mxfp8`."""
+    return _mx.swiglu_quantize_t("mxfp8", 1, torch.float8_e4m3fn, quantize_mxfp8_t, gu)
+
+
+def swiglu_bwd_quantize_mxfp8_dual(gu: torch.Tensor, dh: torch.Tensor):
+    """``quantize_mxfp8_dual(dgu)`` of the SwiGLU gradient ``dgu = [dg | du]``
+    ``[T, 2F]`` for ``gu`` ``[T, 2F]`` and ``dh`` ``[T, F]`` (bf16, ``T`` and ``F``
+    multiples of 32), bit for bit, from one read of ``gu`` and ``dh`` and without
+    ``dgu`` in memory; see :func:`swiglu_quantize_mxfp8`."""
+    return _mx.swiglu_bwd_quantize_dual("mxfp8", 1, torch.float8_e4m3fn, quantize_mxfp8_dual, gu, dh)
+
+
 def _check_pair(q: torch.Tensor, s: torch.Tensor, qn: str, sn: str) -> None:
     _mx.check_pair(q, s, qn, sn, torch.float8_e4m3fn, "float8_e4m3fn", 1)
 

@@ -62,23 +62,11 @@
 #include "mx_gemm_core.h"
 #include "mx_quantize.h"
 #include "mxfp4_format.h"
+#include "mx_formats.h"   // struct E2m1, the element format of the shared quantiser kernels
 
 namespace {
 
 using namespace mxk::mx;
-
-// ---------------------------------------------------------------------------
-// Quantiser
-// ---------------------------------------------------------------------------
-// The element format of the shared quantiser kernels (mx_quantize.h): one
-// packed dword per lane.
-struct E2m1 {
-  static constexpr int kBits = 4;
-  static constexpr float kMax = mxfp4::kMax;
-  __device__ static int block_exp(float amax) { return mxfp4::block_exp(amax); }
-  __device__ static float inv_scale(int e) { return mxfp4::block_inv_scale(e); }
-  __device__ static uint32_t convert(float v) { return mxfp4::f32_to_e2m1(v); }
-};
 
 // ---------------------------------------------------------------------------
 // GEMM

@@ -44,53 +44,11 @@
 // builtin: it places the hazard waits and the accumulators.
 #include "mx_gemm_core.h"
 #include "mx_quantize.h"
+#include "mx_formats.h"   // struct E4m3, the element format of the shared quantiser kernels
 
 namespace {
 
 using namespace mxk::mx;
-
-// ---------------------------------------------------------------------------
-// Quantiser
-// ---------------------------------------------------------------------------
-// The element format of the shared quantiser kernels (mx_quantize.h).
-struct E4m3 {
-  static constexpr int kBits = 8;
-  static constexpr float kMax = 448.f;
-
-  // floor(log2(amax)) - 8 clamped to [-127, 127]; 0 for amax == 0
-  __device__ static int block_exp(float amax) {
-    uint32_t u;
-    __builtin_memcpy(&u, &amax, 4);
-    if (u == 0) return 0;
-    const int e = static_cast<int>(u >> 23) - 127 - 8;   // an fp32 subnormal lands below -127
-    return e < -127 ? -127 : e;                           // bf16 input: e <= 119
-  }
-
-  __device__ static float inv_scale(int e) {   // 2^-e
-    return __uint_as_float(static_cast<uint32_t>(127 - e) << 23);
-  }
-
-  // RNE of a finite fp32 with |v| <= 448 to an e4m3fn byte.
-  __device__ static uint32_t convert(float v) {
-    uint32_t u;
-    __builtin_memcpy(&u, &v, 4);
-    const uint32_t sign = (u >> 24) & 0x80u;
-    u &= 0x7FFFFFFFu;
-    uint32_t r;
-    if (u >= 0x3C800000u) {                 // >= 2^-6: a normal e4m3
-      u += 0x7FFFFu + ((u >> 20) & 1u);     // round to 3 mantissa bits, ties to even
-      r = (u >> 20) - (120u << 3);          // rebias 127 -> 7
-    } else {                                // subnormal: units of 2^-9
-      float a;
-      __builtin_memcpy(&a, &u, 4);
-      a += 16384.0f;                        // 2^14: the sum's last bit is 2^-9
-      uint32_t b;
-      __builtin_memcpy(&b, &a, 4);
-      r = b - 0x46800000u;
-    }
-    return r | sign;
-  }
-};
 
 // ---------------------------------------------------------------------------
 // GEMM

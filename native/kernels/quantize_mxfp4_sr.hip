@@ -34,21 +34,11 @@
 #include "mx_quantize.h"
 #include "mx_philox.h"
 #include "mxfp4_format.h"
+#include "mx_formats.h"   // struct E2m1Sr
 
 namespace {
 
 using namespace mxk::mx;
-
-struct E2m1Sr {
-  static constexpr int kBits = 4;   // no kMax: the block exponent does not clip
-  __device__ static int block_exp(float amax) { return mxfp4::block_exp_noclip(amax); }
-  __device__ static float inv_scale(int e) { return mxfp4::block_inv_scale(e); }
-  __device__ static void random(const SrLane& l, uint32_t (&r)[4]) {
-    philox::philox4x32_10(l.g, l.i, 0u, 0u, static_cast<uint32_t>(l.seed),
-                          static_cast<uint32_t>(l.seed >> 32), r);
-  }
-  __device__ static uint32_t convert(float v, uint32_t u16) { return mxfp4::f32_to_e2m1_sr(v, u16); }
-};
 
 }  // namespace
 
