@@ -32,10 +32,11 @@ __device__ __forceinline__ void x2_trickle(f32x4_t (&acc)[8][8], bf16x8_t (&f0a)
   const H h0{{}, buf[Q], tp + Q * tstride};
   const H h1{{}, buf[Q + 1], tp + (Q + 1) * tstride};
   // K-tile 0: the 16 burst stores and its own trickle store are younger than stage 1
-  x2_ktile_s<SCHED, AN, BN, 0, 1, (Q == 0 ? 17 : 1), H>(acc, f0a, f0b, f1a, f1b, smem, oa, ob, wm,
-                                                        wn, sa, sb, wave, 0, h0);
-  x2_ktile_s<SCHED, AN, BN, 1, 1, 1, H>(acc, f0a, f0b, f1a, f1b, smem, oa, ob, wm, wn, sa + ka,
-                                        sb + kb, wave, 0, h1);
+  // (pieces through dma16m, as the record was measured: QDMA false)
+  x2_ktile_s<SCHED, AN, BN, 0, 1, (Q == 0 ? 17 : 1), H, false>(acc, f0a, f0b, f1a, f1b, smem, oa, ob,
+                                                               wm, wn, sa, sb, wave, 0, h0);
+  x2_ktile_s<SCHED, AN, BN, 1, 1, 1, H, false>(acc, f0a, f0b, f1a, f1b, smem, oa, ob, wm, wn,
+                                               sa + ka, sb + kb, wave, 0, h1);
   sa += 2 * ka;
   sb += 2 * kb;
   if constexpr (Q + 2 < NB)
@@ -114,14 +115,16 @@ mxk_gemm_bf16_x2t_kernel(const uint16_t* __restrict__ A, const uint16_t* __restr
       s = NB;
     }
     for (; s + 2 <= ns - 2; s += 2) {
-      x2_ktile_s<SCHED, AN, BN, 0, 1>(acc, f0a, f0b, f1a, f1b, smem, oa, ob, wm, wn, sa, sb, wave);
-      x2_ktile_s<SCHED, AN, BN, 1, 1>(acc, f0a, f0b, f1a, f1b, smem, oa, ob, wm, wn, sa + ka,
-                                      sb + kb, wave);
+      x2_ktile_s<SCHED, AN, BN, 0, 1, 0, mxk::NoHook, false>(acc, f0a, f0b, f1a, f1b, smem, oa, ob, wm,
+                                                             wn, sa, sb, wave);
+      x2_ktile_s<SCHED, AN, BN, 1, 1, 0, mxk::NoHook, false>(acc, f0a, f0b, f1a, f1b, smem, oa, ob, wm,
+                                                             wn, sa + ka, sb + kb, wave);
       sa += 2 * ka;
       sb += 2 * kb;
     }
     if (s < ns - 2) {
-      x2_ktile_s<SCHED, AN, BN, 0, 1>(acc, f0a, f0b, f1a, f1b, smem, oa, ob, wm, wn, sa, sb, wave);
+      x2_ktile_s<SCHED, AN, BN, 0, 1, 0, mxk::NoHook, false>(acc, f0a, f0b, f1a, f1b, smem, oa, ob, wm,
+                                                             wn, sa, sb, wave);
       ++s;
     }
     x2_ktile_s<SCHED, AN, BN, 2, 2>(acc, f0a, f0b, f1a, f1b, smem, oa, ob, wm, wn, 0, 0, wave, s & 1);

@@ -104,7 +104,12 @@
 //  56 w4j   26 with an L2 prefetch of stage s+4 per K-tile (gemm_tn_core.h
 //           L2Prefetch; for HBM-cold operands): -1.5..-3 % warm, -1.7 % cold
 //           (profiles/r4_gemm/cold_vs_warm_prefetch56.txt)
-//  29-30    gemm_bf16_ring.hip: a ring of 4 / 5 32-deep k slots, one
+//  59 w4k   52 with its LDS-DMA pieces through the builtin: the M0 write and
+//           the compiler's nop in the piece's own MFMA gap (52 until its M0
+//           writes moved to gaps of their own, mxk::m0_put / dma16q);
+//           bit-identical, -1.2..-1.9 % at 8192^3 / 16384^3 in one process
+//           (profiles/dma_gaps/)
+//  29-30   gemm_bf16_ring.hip: a ring of 4 / 5 32-deep k slots, one
 //           barrier per k-step, refills 4-5 steps ahead: -9 % at 8192^3,
 //           -23 % at 16384^3 (a k32 slot row is half a 128-B line, so each
 //           line is fetched twice; profiles/r3_gemm/)
@@ -482,7 +487,7 @@ MXK_API void mxk_gemm_stagger_part_xcd(int b, int T, int cx, int* out) {
 }
 
 namespace {
-constexpr int kNumVariants = 59;
+constexpr int kNumVariants = 60;
 constexpr int kDefaultVariant = 52;
 constexpr int kNarrowCVariant = GEMM_TN_NARROW_C;
 constexpr const char* kVariantNames[kNumVariants] = {
@@ -495,7 +500,7 @@ constexpr const char* kVariantNames[kNumVariants] = {
     "w4j_ldsst_map16x2", "w4j_ldsst_rot_xcd", "diag_stamps", "w4i_ldsst_full_template",
     "w4k_1bar_a3_ldsst", "diag_w4k_nodma", "diag_w4k_noreads", "diag_w4k_nowait",
     "diag_w4k_mfma_only", "w4k_border", "diag_w4k_nostore", "w4j_stagger", "w4j_stagger_cached", "w4j_l2pf", "w4j_stagger_xcd",
-    "w4p_persistent"};
+    "w4p_persistent", "w4k_border_builtin_dma"};
 
 }  // namespace
 #ifdef MXK_GEMM_EXPERIMENTS
@@ -521,6 +526,9 @@ void launch_256(int v, int nwg, hipStream_t stream, const void* A, const void* B
       MXK_TN((mxk_gemm_bf16_tn_w4p<1, 1>), cus > 0 && cus < nwg ? cus : nwg);
       break;
     }
+    // 52 with its pieces through the builtin: the M0 write and the compiler's
+    // nop in the piece's own MFMA gap (52 up to this record; bit-identical)
+    case 59: MXK_TN((mxk_gemm_bf16_tn_w4k<1, 4, 0, 1, false>), nwg); break;
 #endif
     case 1: MXK_TN((mxk_gemm_bf16_tn_w4j<1, 0>), nwg); break;
     case 6: MXK_TN((mxk_gemm_bf16_tn_w4j<1, 2>), nwg); break;

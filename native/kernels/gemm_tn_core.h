@@ -54,6 +54,15 @@ struct DmaK {
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)(lds_op + (p * 4 + wave_s) * 1024),
                                              16, voff[p], k_bytes, 0, 0);
   }
+  // The one-barrier K-tile: the piece bare (mxk::dma16q), its LDS address
+  // dst32 written to M0 in an MFMA gap ahead of it (mxk::m0_put)
+  mxk::u32x4 rs;                 // rsrc again, as the inline asm takes it
+  __device__ __forceinline__ static uint32_t dst32(const char* lds_op, int p, int wave_s) {
+    return mxk::lds_addr32(lds_op) + (p * 4 + wave_s) * 1024;
+  }
+  __device__ __forceinline__ void issue_q(int p, int k_bytes) const {
+    mxk::dma16q(rs, voff[p], k_bytes);
+  }
 };
 
 __device__ __forceinline__ DmaK make_dmak(const uint16_t* src, int ld, int row0, int lane,
@@ -62,6 +71,7 @@ __device__ __forceinline__ DmaK make_dmak(const uint16_t* src, int ld, int row0,
   const uint16_t* base = src + static_cast<size_t>(row0) * ld;
   d.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(base), 0, 256 * ld * 2,
                                              0x00020000);
+  d.rs = mxk::make_rsrc(base, 256u * ld * 2u);
   const int r = lane >> 3;
   // swm 7: the full XOR swizzle; 4: only the 64-B halves swap (each 4-lane
   // group keeps an ascending 64-B source run); 0: linear (A/B variants 37/38)
@@ -469,6 +479,11 @@ mxk_gemm_bf16_tn_w4j_stag(const uint16_t* __restrict__ A, const uint16_t* __rest
 //                  of s+2 stay in flight) + the barrier
 //   m 93..123      next K-tile's k-half-0 fragments (stage s+1), SchedHB order
 //   m 94..115      DMA of stage s+2, B pieces -> B slot s%2
+//   m 31..59 /4    M0 <- LDS address of the A piece two MFMAs on (empty gaps)
+//   m 91..113      M0 <- LDS address of the next B piece: between the piece
+//                  before and its own, in an empty gap where there is one
+//                  (91, 100, 108, 113), else beside a fragment read (95, 98,
+//                  103, 106); never beside a piece
 // The stage slots repeat every 6 K-tiles; the loop is unrolled by 6 so every
 // LDS address is a compile-time offset.
 struct SchedA3 {
@@ -485,6 +500,11 @@ struct SchedA3 {
          : m == 110 ? 6 : m == 115 ? 7 : -1;
   }
   __host__ __device__ static constexpr int k0(int m) { return SchedHB::k0(m); }
+  __host__ __device__ static constexpr int am0(int m) { return adma(m + 2); }
+  __host__ __device__ static constexpr int bm0(int m) {
+    return m == 91 ? 0 : m == 95 ? 1 : m == 98 ? 2 : m == 100 ? 3 : m == 103 ? 4 : m == 106 ? 5
+         : m == 108 ? 6 : m == 113 ? 7 : -1;
+  }
 };
 
 constexpr int A3_SLOT = W4B_OP_BYTES;          // 32 KiB
@@ -499,8 +519,12 @@ constexpr int A3_LDS = 5 * A3_SLOT;            // 160 KiB
 // ORDER 1: the B fragment is the outer MFMA loop (srcA held for 8 MFMAs,
 // srcB changing - hipBLASLt's operand order) instead of the A fragment.
 // SPLITA: A fragments 0-3 at a_base, 4-7 at a_hi (the w13 SwiGLU kernel).
+// QDMA: the pieces bare with their M0 writes in gaps of their own (above);
+// false: the builtin, whose M0 write (and the compiler's nop) shares the
+// piece's gap (A/B record 59).  M0 belongs to the K-tile from its first
+// m0_put to its last piece: a HOOK must not use it.
 template <int AS, int BS, int MODE, class HOOK = NoHook, int ABL = 0, int ORDER = 0,
-          bool SPLITA = false>
+          bool SPLITA = false, bool QDMA = true>
 __device__ __forceinline__ void w4k_ktile(f32x4_t (&acc)[8][8], bf16x8_t (&f0a)[8],
                                           bf16x8_t (&f0b)[8], bf16x8_t (&f1a)[8],
                                           bf16x8_t (&f1b)[8], char* smem, int a_base, int b_base,
@@ -529,11 +553,18 @@ __device__ __forceinline__ void w4k_ktile(f32x4_t (&acc)[8][8], bf16x8_t (&f0a)[
         if (h == 0) mfma_16x16x32_agpr(acc[i][j], f0b[j], f0a[i]);
         else mfma_16x16x32_agpr(acc[i][j], f1b[j], f1a[i]);
         hook(m);
+        if constexpr (QDMA && MODE == 1 && !(ABL & 1)) {
+          if (S::am0(m) >= 0) mxk::m0_put(DmaK::dst32(RA, S::am0(m), wave_s));
+          if (S::bm0(m) >= 0) mxk::m0_put(DmaK::dst32(XB, S::bm0(m), wave_s));
+        }
         if (!(ABL & 2) && S::a1(m) >= 0)
           f1a[S::a1(m)] = lds_read_b128(XA + aoff(S::a1(m)) + off_k1);
         if (!(ABL & 2) && S::b1(m) >= 0)
           f1b[S::b1(m)] = lds_read_b128(XB + b_base + S::b1(m) * SUB + off_k1);
-        if (!(ABL & 1) && MODE == 1 && S::adma(m) >= 0) dma_a.issue(RA, S::adma(m), kb2, wave_s);
+        if (!(ABL & 1) && MODE == 1 && S::adma(m) >= 0) {
+          if constexpr (QDMA) dma_a.issue_q(S::adma(m), kb2);
+          else dma_a.issue(RA, S::adma(m), kb2, wave_s);
+        }
         if (!(ABL & 4) && MODE != 3 && m == S::WB) {
           hook.at(4);
           __builtin_amdgcn_s_waitcnt(0xC07F);          // this wave's B k1 reads retired
@@ -542,7 +573,10 @@ __device__ __forceinline__ void w4k_ktile(f32x4_t (&acc)[8][8], bf16x8_t (&f0a)[
           __builtin_amdgcn_s_barrier();
           hook.at(5);
         }
-        if (!(ABL & 1) && MODE == 1 && S::bdma(m) >= 0) dma_b.issue(XB, S::bdma(m), kb2, wave_s);
+        if (!(ABL & 1) && MODE == 1 && S::bdma(m) >= 0) {
+          if constexpr (QDMA) dma_b.issue_q(S::bdma(m), kb2);
+          else dma_b.issue(XB, S::bdma(m), kb2, wave_s);
+        }
         if (!(ABL & 2) && MODE != 3 && S::k0(m) >= 0) {
           const int r = S::k0(m);
           if (r < 8) f0b[r] = lds_read_b128(YB + b_base + r * SUB + off_k0);
@@ -564,7 +598,7 @@ __device__ __forceinline__ void w4k_ktile(f32x4_t (&acc)[8][8], bf16x8_t (&f0a)[
 // PRE_VM: the vmcnt that, in a pre call, leaves stage 1's 16 DMA pieces and
 // the previous epilogue's stores in flight but waits for stage 0 (32 plain
 // C stores: 48; at most 63)
-template <int ABL = 0, int ORDER = 0, bool SPLITA = false, int PRE_VM = 48>
+template <int ABL = 0, int ORDER = 0, bool SPLITA = false, int PRE_VM = 48, bool QDMA = true>
 __device__ __forceinline__ void w4k_mainloop(f32x4_t (&acc)[8][8], char* smem, const DmaK& dma_a,
                                              const DmaK& dma_b, int a_base, int a_hi, int b_base,
                                              int ns, int lane, int wave_s, bool pre = false) {
@@ -618,9 +652,9 @@ __device__ __forceinline__ void w4k_mainloop(f32x4_t (&acc)[8][8], char* smem, c
   int s = 0;
   int kb = 2 * BK * 2;
 #define MXK_W4K(as_, bs_)                                                                       \
-  w4k_ktile<as_, bs_, 1, NoHook, ABL, ORDER, SPLITA>(acc, f0a, f0b, f1a, f1b, smem, a_base, b_base, \
-                                                     off_k0, off_k1, dma_a, dma_b, kb, wave_s, 0, 0, \
-                                                     NoHook{}, a_hi);                            \
+  w4k_ktile<as_, bs_, 1, NoHook, ABL, ORDER, SPLITA, QDMA>(                                     \
+      acc, f0a, f0b, f1a, f1b, smem, a_base, b_base, off_k0, off_k1, dma_a, dma_b, kb, wave_s, 0, 0, \
+      NoHook{}, a_hi);                                                                           \
   kb += BK * 2;
   for (; s + 6 <= ns - 2; s += 6) {
     MXK_W4K(0, 0) MXK_W4K(1, 1) MXK_W4K(2, 0) MXK_W4K(0, 1) MXK_W4K(1, 0) MXK_W4K(2, 1)
@@ -648,7 +682,7 @@ __device__ __forceinline__ void w4k_mainloop(f32x4_t (&acc)[8][8], char* smem, c
   mxk::mfma_drain(acc);
 }
 
-template <int MAP, int EPI, int ABL = 0, int ORDER = 0>
+template <int MAP, int EPI, int ABL = 0, int ORDER = 0, bool QDMA = true>
 __global__ void __launch_bounds__(W4_THREADS, 1)
 mxk_gemm_bf16_tn_w4k(const uint16_t* __restrict__ A, const uint16_t* __restrict__ Bt,
                      uint16_t* __restrict__ C, int M, int N, int K, int lda, int ldb, int ldc,
@@ -667,8 +701,8 @@ mxk_gemm_bf16_tn_w4k(const uint16_t* __restrict__ A, const uint16_t* __restrict_
   const DmaK dma_b = make_dmak(Bt, ldb, n0, lane, wave_s);
   constexpr int SUB = 2048;
   f32x4_t acc[8][8];
-  w4k_mainloop<ABL, ORDER>(acc, smem, dma_a, dma_b, wm * 8 * SUB, 0, wn * 8 * SUB, K / BK, lane,
-                           wave_s);
+  w4k_mainloop<ABL, ORDER, false, 48, QDMA>(acc, smem, dma_a, dma_b, wm * 8 * SUB, 0, wn * 8 * SUB,
+                                            K / BK, lane, wave_s);
 
   if constexpr (ABL & 8) {
     return;

@@ -77,9 +77,15 @@ struct XOp<false> {
     sm = smem;
     sm32 = smem32;
   }
+  __device__ __forceinline__ uint32_t dst32(char* lds, int p, int wave) const {
+    return sm32 + static_cast<uint32_t>(lds - sm) + (p * 4 + wave) * 1024;
+  }
   __device__ __forceinline__ void issue_s(char* lds, int p, uint32_t soff, int wave) const {
-    mxk::dma16m(rsrc, sm32 + static_cast<uint32_t>(lds - sm) + (p * 4 + wave) * 1024, voff[p],
-                soff);
+    mxk::dma16m(rsrc, dst32(lds, p, wave), voff[p], soff);
+  }
+  // K loop: M0 <- dst32 of the piece in a gap ahead of it (mxk::m0_put), then the bare piece
+  __device__ __forceinline__ void issue_q(int p, uint32_t soff) const {
+    mxk::dma16q(rsrc, voff[p], soff);
   }
   // fragment of 16-row subtile i (i = 0..15 over the 256 rows), k-step ks
   __device__ __forceinline__ bf16x8_t frag(const char* lds, int i, int ks) const {
@@ -129,9 +135,14 @@ struct XOp<true> {
     sm = smem;
     sm32 = smem32;
   }
+  __device__ __forceinline__ uint32_t dst32(char* lds, int p, int wave) const {
+    return sm32 + static_cast<uint32_t>(lds - sm) + p * TGROUP + wave * 1024;
+  }
   __device__ __forceinline__ void issue_s(char* lds, int p, uint32_t soff, int wave) const {
-    mxk::dma16m(rsrc, sm32 + static_cast<uint32_t>(lds - sm) + p * TGROUP + wave * 1024, voff[p],
-                soff);
+    mxk::dma16m(rsrc, dst32(lds, p, wave), voff[p], soff);
+  }
+  __device__ __forceinline__ void issue_q(int p, uint32_t soff) const {
+    mxk::dma16q(rsrc, voff[p], soff);
   }
   __device__ __forceinline__ bf16x8_t frag(const char* lds, int i, int ks) const {
     const char* p = lds + roff[i & 3] + 32 * (i & ~3) + ks * KSTEP_T;
@@ -280,8 +291,16 @@ mxk_gemm_bf16_x_kernel(const uint16_t* __restrict__ A, const uint16_t* __restric
 // vmcnt: the vector-memory ops beyond the schedule's own pieces that are
 // younger than the stage being waited for (the trickle kernel's C stores sit
 // among the DMA pieces); HOOK(m) runs after MFMA m.
+// The pieces go out bare (mxk::dma16q), each with its LDS address written to
+// M0 in an earlier, piece-free MFMA gap (S::am0 / S::bm0): nothing else in a
+// MODE 1 K-tile uses M0, and no descriptor or offset SGPR of a piece is
+// VALU-written there (both audited on the listing, tests/test_isa_dma_gaps.py
+// and test_isa_hazards.py).  A HOOK must not touch M0 in a MODE 1 K-tile.
+// QDMA false: every piece through dma16m, M0 write and nop beside it (the
+// trickle-store A/B records keep it: they sit at the VGPR limit, and the
+// bare pieces tipped one of them into spills).
 template <class S, bool AN, bool BN, int PAR, int MODE, int PRIO = 0, int VMD = 0,
-          class HOOK = mxk::NoHook, int ORDER = 0>
+          class HOOK = mxk::NoHook, int ORDER = 0, bool QDMA = true>
 __device__ __forceinline__ void x2_ktile(f32x4_t (&acc)[8][8], bf16x8_t (&f0a)[8],
                                          bf16x8_t (&f0b)[8], bf16x8_t (&f1a)[8],
                                          bf16x8_t (&f1b)[8], char* smem, const XOp<AN>& oa,
@@ -309,11 +328,21 @@ __device__ __forceinline__ void x2_ktile(f32x4_t (&acc)[8][8], bf16x8_t (&f0a)[8
         if (S::a1(m) >= 0) f1a[S::a1(m)] = oa.frag(X, wm * 8 + S::a1(m), 1);
         if (MODE == 1 && m == S::W1) __builtin_amdgcn_s_waitcnt(0xC07F);
         if (MODE == 1 && m == S::B1) __builtin_amdgcn_s_barrier();
-        if (MODE == 1 && S::adma(m) >= 0) oa.issue_s(X, S::adma(m), soa, wave);
+        if constexpr (QDMA && MODE == 1) {
+          if (S::am0(m) >= 0) mxk::m0_put(oa.dst32(X, S::am0(m), wave));
+          if (S::bm0(m) >= 0) mxk::m0_put(ob.dst32(X + A_BYTES, S::bm0(m), wave));
+        }
+        if (MODE == 1 && S::adma(m) >= 0) {
+          if constexpr (QDMA) oa.issue_q(S::adma(m), soa);
+          else oa.issue_s(X, S::adma(m), soa, wave);
+        }
         if (S::b1(m) >= 0) f1b[S::b1(m)] = ob.frag(X + A_BYTES, wn * 8 + S::b1(m), 1);
         if (MODE == 1 && m == S::W2) __builtin_amdgcn_s_waitcnt(0xC07F);
         if (MODE == 1 && m == S::B2) __builtin_amdgcn_s_barrier();
-        if (MODE == 1 && S::bdma(m) >= 0) ob.issue_s(X + A_BYTES, S::bdma(m), sob, wave);
+        if (MODE == 1 && S::bdma(m) >= 0) {
+          if constexpr (QDMA) ob.issue_q(S::bdma(m), sob);
+          else ob.issue_s(X + A_BYTES, S::bdma(m), sob, wave);
+        }
         if (MODE != 3 && m == S::W3) {
           if constexpr (MODE == 1) mxk::vm_wait_n<S::VM3 + VMD>();
           else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -332,7 +361,8 @@ __device__ __forceinline__ void x2_ktile(f32x4_t (&acc)[8][8], bf16x8_t (&f0a)[8
 
 // SCHED bit 0: hipBLASLt's positions (SchedHB, no raised priority), else the
 // kernel's own (SchedX2, raised priority); bit 1: B-outer MFMA order
-template <int SCHED, bool AN, bool BN, int PAR, int MODE, int VMD = 0, class HOOK = mxk::NoHook>
+template <int SCHED, bool AN, bool BN, int PAR, int MODE, int VMD = 0, class HOOK = mxk::NoHook,
+          bool QDMA = true>
 __device__ __forceinline__ void x2_ktile_s(f32x4_t (&acc)[8][8], bf16x8_t (&f0a)[8],
                                            bf16x8_t (&f0b)[8], bf16x8_t (&f1a)[8],
                                            bf16x8_t (&f1b)[8], char* smem, const XOp<AN>& oa,
@@ -341,7 +371,7 @@ __device__ __forceinline__ void x2_ktile_s(f32x4_t (&acc)[8][8], bf16x8_t (&f0a)
                                            const HOOK& hook = HOOK{}) {
   constexpr bool HB = (SCHED & 1) == 1;
   using S = std::conditional_t<HB, mxk::SchedHB, mxk::SchedX2>;
-  x2_ktile<S, AN, BN, PAR, MODE, !HB, VMD, HOOK, (SCHED >> 1) & 1>(
+  x2_ktile<S, AN, BN, PAR, MODE, !HB, VMD, HOOK, (SCHED >> 1) & 1, QDMA>(
       acc, f0a, f0b, f1a, f1b, smem, oa, ob, wm, wn, soa, sob, wave, par, hook);
 }
 

@@ -209,6 +209,27 @@ __device__ __forceinline__ void dma16m(const u32x4& rsrc, uint32_t lds_addr, uin
                : "memory");
 }
 
+// The two halves of dma16m apart, for the GEMM K loops: there an MFMA gap
+// that carries a piece already runs past the MFMA's 16 cycles, so the M0
+// write beside it (and the nop) costs its whole issue time, while in an empty
+// gap it is nearly free.  m0_put writes the piece's LDS address to M0 in an
+// MFMA gap ahead of the piece; dma16q issues the piece bare: no nop, no M0
+// handling.  The MFMA between the two is the M0 -> LDS-DMA wait state.
+// Only where nothing else uses M0 between the two (a K loop whose every
+// piece goes through dma16q; tests/test_isa_dma_gaps.py reads it off the
+// listing), and where no VALU instruction writes a descriptor or offset SGPR
+// (no s_nop 4: tests/test_isa_hazards.py, valu_sgpr_to_vmem).
+__device__ __forceinline__ void m0_put(uint32_t lds_addr) {
+  uint32_t m0_now;   // an output bound to M0: the compiler knows its own copy of M0 is gone
+  asm volatile("s_mov_b32 m0, %1" : "={m0}"(m0_now) : "s"(lds_addr));
+}
+__device__ __forceinline__ void dma16q(const u32x4& rsrc, uint32_t voff, uint32_t soff) {
+  asm volatile("buffer_load_dwordx4 %0, %1, %2 offen lds"
+               :
+               : "v"(voff), "s"(rsrc), "s"(soff)
+               : "memory");
+}
+
 // 32-bit LDS address of a __shared__ array (a constant after folding)
 template <class T>
 __device__ __forceinline__ uint32_t lds_addr32(T* shared_array) {
@@ -768,6 +789,17 @@ struct SchedHB {
          : m == 103 ? 6 : m == 104 ? 7 : m == 105 ? 8 : m == 106 ? 9 : m == 109 ? 10
          : m == 112 ? 11 : m == 114 ? 12 : m == 117 ? 13 : m == 120 ? 14 : m == 123 ? 15 : -1;
   }
+  // M0 writes (mxk::m0_put) of the pieces, each in an empty gap between the
+  // previous piece and its own (the layout kernel; the TN w4j K-tile issues
+  // its pieces through the builtin)
+  __host__ __device__ static constexpr int am0(int m) {
+    return m == 19 ? 0 : m == 23 ? 1 : m == 26 ? 2 : m == 29 ? 3 : m == 32 ? 4 : m == 49 ? 5
+         : m == 53 ? 6 : m == 56 ? 7 : -1;
+  }
+  __host__ __device__ static constexpr int bm0(int m) {
+    return m == 59 ? 0 : m == 62 ? 1 : m == 83 ? 2 : m == 86 ? 3 : m == 88 ? 4 : m == 90 ? 5
+         : m == 99 ? 6 : m == 121 ? 7 : -1;
+  }
 };
 
 // The layout kernel's own positions (gemm_x2_core.h x2_ktile, SCHED bit 0
@@ -780,6 +812,7 @@ struct SchedHB {
 //   m 57..99 /6   DMA of stage s+2, B pieces -> X.B
 //   m 96          vmcnt(15) + barrier #3 (stage s+1 in Y landed everywhere)
 //   m 97..127 odd next k-half-0 fragments from Y (B, then A)
+//   m 22..50 /4, 56..98 /6   M0 <- LDS address of the piece one MFMA on
 struct SchedX2 {
   static constexpr int W1 = 19, B1 = 19, W2 = 55, B2 = 55, W3 = 96, VM3 = 15, B3 = 96;
   __host__ __device__ static constexpr int a1(int m) { return m < 16 && (m & 1) ? m >> 1 : -1; }
@@ -795,6 +828,9 @@ struct SchedX2 {
   __host__ __device__ static constexpr int k0(int m) {
     return m > 96 && (m & 1) ? (m - 97) >> 1 : -1;
   }
+  // M0 writes of the pieces: the (empty) gap before each piece's own
+  __host__ __device__ static constexpr int am0(int m) { return adma(m + 1); }
+  __host__ __device__ static constexpr int bm0(int m) { return bdma(m + 1); }
 };
 
 // SCHED 3 ("HB-earlyB"): SchedHB with every B piece of stage s+2 issued
